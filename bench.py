@@ -36,6 +36,20 @@ valu: the committed rocprofv3 PMC entry (profiles/pmc_traffic.json, FETCH_SIZE x
 per the gfx950 note + WRITE_SIZE; SQ counters) of this workload, frame batch and
 kernel build hash; null (with the reason, and a warning) when stale.
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) does only what `value` needs:
+set up, warm up, time the N steps, write the outputs (--dump-outputs), print the line.
+--full adds the secondary measurements, each a run of its own: the single-frame,
+display-cadence and reference-pattern timings (N=1), the weak-scaling run (N>1) and the
+CPU baseline (the oracle on a sample of the same frame; N=1).
+
+The timed steps are always frames 1..N of a fresh accumulation (the accumulation is reset
+after the warmup and settle frames, whose number depends on the clock), so with the same
+arguments a run traces the same rays and ends with the same buffers. --dump-outputs DIR
+writes what the last timed step left, as a caller reads it back (rank 0's
+read_accumulation and read_output), to DIR/accumulation.npy (H x W x RGBA, float32) and
+DIR/output_rgba8.npy (H x W x RGBA, the packed RGBA8 bytes as float32); above
+DUMP_BYTES_MAX in all, the same fixed seeded sample of pixels of each (n x RGBA).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -62,6 +76,8 @@ KERNEL_NAMES = {"path": "rt_pathtrace_kernel", "primary": "rt_primary_kernel", "
 # The reference computes a frame every >= 0.8 ms and displays every >= 5 ms
 # (src/main.rs:88-92, 365-375): about 6 computed frames per displayed image.
 DISPLAY_CADENCE_FRAMES = 6
+DUMP_BYTES_MAX = 60_000_000  # --dump-outputs: all arrays together, on disk
+DUMP_SAMPLE_SEED = 0
 
 
 def log(*a):
@@ -160,6 +176,22 @@ def cpu_baseline(scene, bounces, min_seconds: float, sample_world: int):
     }
 
 
+def dump_outputs(directory: Path, r) -> None:
+    """--dump-outputs: the renderer's accumulation and packed output as its caller reads them
+    back, as float32 .npy files. Both arrays hold the same pixels: all of
+    them, or (above DUMP_BYTES_MAX in all) a fixed seeded sample in ascending pixel order."""
+    acc = r.read_accumulation().reshape(-1, 4)
+    rgba = np.ascontiguousarray(r.read_output()).view(np.uint8).reshape(-1, 4).astype(np.float32)
+    shape = (r.height, r.width, 4)
+    keep = DUMP_BYTES_MAX // (2 * 16)  # two arrays of 4 x float32 per pixel
+    if acc.shape[0] > keep:
+        px = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(acc.shape[0], keep, replace=False))
+        acc, rgba, shape = acc[px], rgba[px], (keep, 4)
+    directory.mkdir(parents=True, exist_ok=True)
+    for name, a in (("accumulation", acc), ("output_rgba8", rgba)):
+        np.save(directory / f"{name}.npy", np.ascontiguousarray(a.reshape(shape), np.float32))
+
+
 def default_frame_batch(world: int, steps: int) -> int:
     """Frames per launch: the timed steps split into launches of at most 32N frames
     (64 at most), as evenly as they go -- 20 steps at N=1 are one 20-frame launch,
@@ -185,14 +217,21 @@ def main() -> int:
     ap.add_argument("--bounces", type=int, default=None)
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="after the warmup steps, keep rendering untimed frames for this long (GPU clock ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements, each a run of its own: the cadence timings "
+                         "(N=1), the weak-scaling run (N>1) and the CPU baseline (N=1); off: only what "
+                         "`value` needs")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one left (rank 0's accumulation and "
+                         "packed output, as read back) to DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-sample-world", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true",
                     help="N>1: leave the RCCL gather of the image to rank 0 out of the timed region")
-    ap.add_argument("--no-weak", action="store_true", help="N>1: skip the secondary weak-scaling measurement")
+    ap.add_argument("--no-weak", action="store_true", help="--full, N>1: skip the secondary weak-scaling measurement")
     ap.add_argument("--no-cadences", action="store_true",
-                    help="N=1: skip the secondary single-frame and display-cadence timings")
+                    help="--full, N=1: skip the secondary single-frame and display-cadence timings")
     ap.add_argument("--gather", choices=["image", "accumulation"], default="accumulation",
                     help="N>1: the payload of the gather in the timed region: the RGBA32F accumulation "
                          "(16 B/px, the north star's 'RCCL gather of the accumulated RGBA buffer'; default) or "
@@ -319,6 +358,9 @@ def main() -> int:
             # loop has done by its second frame
             gather_frame(r, 0, "accumulation")
             gather_frame(r, 0, "image")
+        # the timed steps are frames 1..steps of a fresh accumulation whatever the settle loop
+        # rendered: the same rays and the same final buffers from run to run (--dump-outputs)
+        r.reset_accumulation()
         barrier_sync()
         r.reset_ray_count()
         r.reset_timing()
@@ -463,6 +505,9 @@ def main() -> int:
                     t_gather_image_max=t_gather if args.gather == "image" else 0.0, rays_total=float(rays_total))
 
     if args.driver == "group":
+        if args.dump_outputs is not None:
+            log("--dump-outputs reads the frame back through Renderer: not with --driver group")
+            return 2
         if world != 1:
             log("--driver group drives every device from one process: run it without torch.distributed.run")
             return 2
@@ -471,11 +516,13 @@ def main() -> int:
     fb = args.frame_batch or default_frame_batch(world, args.steps)
     main_run = run_group(fb) if args.driver == "group" else run(args.scaling, fb)
     r = main_run["r"]
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, r)
     if (main_run["gathered"] and os.environ.get("RT_BENCH_VERIFY_GATHER") == "1" and rank == 0
             and args.driver != "group"):
         # the assembled tile-split image must equal a 1-GPU render of the same frames
         with Renderer(main_run["scene"], device=device) as ref:
-            for _ in range(args.warmup + main_run["settle_frames"] + args.steps):
+            for _ in range(args.steps):  # the timed steps start from a reset accumulation
                 ref.compute_frame(main_run["bounces"])
             same = np.array_equal(ref.read_accumulation().view(np.uint32), r.read_accumulation().view(np.uint32))
             same = same and np.array_equal(ref.read_output(), r.read_output())
@@ -489,7 +536,7 @@ def main() -> int:
     # displayed every >= 5 ms); one launch per frame (rt_set_frame_batch(1), the reference's
     # one dispatch per compute_frame); launches of 6 frames (the display pacing, submitted).
     cadences = {}
-    if world == 1 and not args.no_cadences and args.driver != "group":
+    if args.full and world == 1 and not args.no_cadences and args.driver != "group":
         for key, batch, pattern in (("ms_per_step_reference_pattern", None, "reference"),
                                     ("ms_per_step_f1", 1, "submit"),
                                     ("ms_per_step_display_cadence", DISPLAY_CADENCE_FRAMES, "submit")):
@@ -497,7 +544,7 @@ def main() -> int:
             c_run["r"].close()
             cadences[key] = c_run["t_total_max"] / args.steps * 1e3
     weak = None
-    if dist_run and args.scaling == "strong" and not args.no_weak and args.driver != "group":
+    if args.full and dist_run and args.scaling == "strong" and not args.no_weak and args.driver != "group":
         w_run = run("weak", args.frame_batch or default_frame_batch(1, args.steps))
         w_run["r"].close()
         weak = {
@@ -647,7 +694,7 @@ def main() -> int:
                 result["value_with_image_gather"] = m["rays_total"] / (m["t_render_max"] + m["t_gather_image_max"]) / 1e6
             if weak is not None:
                 result["weak"] = weak
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline ...")
             result["cpu_baseline"] = cpu_baseline(scene, bounces, args.cpu_seconds, args.cpu_sample_world)
         print(json.dumps(result), flush=True)

@@ -38,7 +38,7 @@ def test_gpu_bench_distributed_path_rccl(gpu):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", RT_BENCH_DIST="1", RT_BENCH_VERIFY_GATHER="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), str(ROOT / "bench.py"),
-           "--gpus", "1", "--steps", "4", "--warmup", "2", "--settle-ms", "20", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "4", "--warmup", "2", "--settle-ms", "20", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=280, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,8 +6,8 @@ scene.py -- SceneObject::new, create_sub_objects, and the edit path
 update_triangles + update_sub_objects under arbitrary rotations, scales and
 translations -- and the chess scene must build to the counts the reference
 asserts (src/main.rs:39-44, :123-128). STL parsing is checked against the
-binary meshes in the committed fixture and, where the reference checkout is
-present (not on the GPU box), against its own 3D_models/*.stl files.
+binary meshes in the committed fixture and against the reference's own
+3D_models/*.stl files (copies under tests/golden/stl/).
 """
 from pathlib import Path
 
@@ -18,7 +18,7 @@ from rust_gpu_raytracing_amd import RtError
 from rust_gpu_raytracing_amd import builder as NB
 from rust_gpu_raytracing_amd import scene as S
 
-REF_MODELS = Path("/root/reference/3D_models")
+REF_MODELS = Path(__file__).resolve().parent / "golden" / "stl"  # the reference's 3D_models/*.stl, as fixtures
 
 
 def chess_meshes():
@@ -147,7 +147,6 @@ endsolid tri
         NB.object_new(np.zeros((1, 3, 3), np.float32), 0.0, [0, 0, 0], [0, 0, 0], 0)  # scale > 0 (:67)
 
 
-@pytest.mark.skipif(not REF_MODELS.is_dir(), reason="reference checkout not present")
 def test_stl_reference_files(native_lib):
     meshes = chess_meshes()
     for name, v in meshes.items():
