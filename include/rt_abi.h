@@ -43,6 +43,9 @@ extern "C" {
 #define RT_API
 #endif
 
+/* History: ... 11 (device display copy, default frame batch), 12 (tuning keys instead of
+ * environment variables); 12, additive: ray queries (rt_trace_rays, rt_trace_rays_device,
+ * rt_pick, rt_query_ray, rt_hit -- nothing earlier changed, so the number stays). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -274,6 +277,83 @@ RT_API int rt_flush(rt_ctx* ctx);
 /* Blocks until all work on the context's stream has finished. */
 RT_API int rt_synchronize(rt_ctx* ctx);
 
+/* ---- ray queries (ABI 12, additive: ray queries) ---------------------------
+ *
+ * "What does this ray hit?" for arbitrary rays, answered by the closest-hit search the
+ * path tracer runs for every path segment (the exact-culling sphere BVH, the certified
+ * triangle accelerator, the brute-force set): trace_ray of the reference
+ * (compute_shader.wgsl:342-353) as a batched call. Every record is bit-identical to the
+ * reference's sweep over all primitives.
+ *
+ * Both records are laid out for 16-byte vector loads and stores. */
+
+/* One ray. Directions need not be unit length; the pads are ignored. 32 bytes. */
+typedef struct rt_query_ray {
+    float origin[3];
+    float _pad0;
+    float direction[3];
+    float _pad1;
+} rt_query_ray;
+
+/* The closest hit of one ray (HitPayload, compute_shader.wgsl:128-137, plus what was hit).
+ * A miss is all-zero apart from t. 64 bytes. */
+#define RT_HIT_MISS 0u
+#define RT_HIT_SPHERE 1u
+#define RT_HIT_TRIANGLE 2u
+typedef struct rt_hit {
+    float t;                 /* hit distance in units of |direction|; 3.4028235e38f on a miss */
+    float position[3];       /* origin + direction * t */
+    float normal[3];         /* unit, facing the ray */
+    float u;                 /* texture coordinates (sphere_texture_coords / object_texture_coords) */
+    float v;
+    uint32_t material_index;
+    uint32_t front_face;     /* 0 or 1 */
+    uint32_t kind;           /* RT_HIT_MISS, RT_HIT_SPHERE, RT_HIT_TRIANGLE */
+    uint32_t index;          /* sphere index as uploaded with rt_update_spheres, or object index */
+    uint32_t sub_object;     /* triangle hits: index into the sub-object buffer; else 0 */
+    uint32_t triangle;       /* triangle hits: index into the triangle buffer; else 0 */
+    uint32_t _reserved;      /* 0 */
+} rt_hit;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is 32 bytes");
+static_assert(sizeof(rt_hit) == 64, "rt_hit is 64 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is 32 bytes");
+_Static_assert(sizeof(rt_hit) == 64, "rt_hit is 64 bytes");
+#endif
+
+/* Traces `count` rays and writes one record per ray, in order.
+ *
+ * A query sees the scene as of the call: after every earlier rt_update_*,
+ * rt_set_object_models and rt_update_objects, with the accelerators prepared exactly as a
+ * dispatch prepares them. It changes nothing a render can observe: not the accumulation,
+ * the output, the accumulation index, the frames queued by rt_compute_frame (they stay
+ * queued: rt_frame_batch reports the same `pending`), rt_ray_count, the timing totals or
+ * the tile schedule. Results do not depend on the brute-force mode, on any rt_set_tuning
+ * key or on triangle pruning modes 0 and 1 (mode 2 is inexact for queries as for frames).
+ *
+ * Exactness holds for the domain the culling bounds are derived for (DESIGN.md §5.2,
+ * §5.3c): finite components, |direction| in [1e-5, 1e5], |origin| <= 1e15. Outside it the
+ * record is unspecified; the search still terminates (the walks' skip links only advance).
+ *
+ * rt_trace_rays: host pointers, synchronous. Rays and records are staged through pinned
+ * memory in chunks of tuning "query_chunk" rays, so `count` is not limited by a scratch
+ * allocation.
+ * rt_trace_rays_device: device pointers on the context's device, 16-byte aligned;
+ * stream-ordered on rt_stream(ctx), no host copy, asynchronous. RT_E_INVALID when either
+ * is not device memory of the context's device.
+ * count == 0 returns RT_OK and launches nothing; NULL pointers with count > 0 are
+ * RT_E_INVALID. */
+RT_API int rt_trace_rays(rt_ctx* ctx, const rt_query_ray* rays, rt_hit* hits, uint64_t count);
+RT_API int rt_trace_rays_device(rt_ctx* ctx, const void* rays_device, void* hits_device, uint64_t count);
+
+/* The closest hit of pixel (x, y)'s un-jittered camera ray: the camera origin plus that
+ * pixel's direction, from the ray buffer (rt_update_ray_directions) or computed from the
+ * camera matrices while rt_update_camera_matrices is in effect. RT_E_INVALID when x or y
+ * is outside the framebuffer. Synchronous. */
+RT_API int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit);
+
 /* Readback (new: the reference only blits output_data to the swapchain,
  * src/renderer.rs:254-283). Synchronous; whole framebuffer, row-major
  * width*height. Pixels of tiles owned by another rank are left as they were
@@ -362,7 +442,10 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "sphere_octants" 1|0, "sphere_box_order" 1|0, "tri_bvh" 1|0 (0: the reference's sweep),
  *   "tri_octants" 1|0, "tri_qnodes" 1|0, "coop_leaves" 1|0, "stage_subs" 1|0,
  *   "primary_pass" -1|0|1 (-1: by scene), "primary_threads" 256|64|128|512|1024,
- *   "primary_waves" 8|0, "primary_tile_major" 1|0.
+ *   "primary_waves" 8|0, "primary_tile_major" 1|0;
+ *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays),
+ *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
+ *   0..2: the highest LDS staging mode of the query kernel, falling back as a dispatch does).
  * RT_E_INVALID for an unknown key or a value out of range. */
 RT_API int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value);
 

@@ -78,7 +78,20 @@ class rt_create_info(ctypes.Structure):
     ]
 
 
+class rt_query_ray(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_float * 3), ("_pad0", ctypes.c_float),
+                ("direction", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
+
+
+class rt_hit(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
+                ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
+                ("front_face", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("index", ctypes.c_uint32),
+                ("sub_object", ctypes.c_uint32), ("triangle", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
+
+
 assert ctypes.sizeof(rt_params) == 48
+assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -113,6 +126,9 @@ SIGNATURES = {
     "rt_read_output": (ctypes.c_int, [_P, _P]),
     "rt_copy_output_to_device": (ctypes.c_int, [_P, _P, _U32]),
     "rt_read_accumulation": (ctypes.c_int, [_P, _P]),
+    "rt_trace_rays": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_trace_rays_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_pick": (ctypes.c_int, [_P, _U32, _U32, _P]),
     "rt_read_output_pitched": (ctypes.c_int, [_P, _P, _U32]),
     "rt_bytes_per_row": (_U32, [_U32, _U32]),
     "rt_ray_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),

@@ -91,9 +91,31 @@ OBJECT_TRANSFORM = np.dtype(
     [("rotation", "<f4", 3), ("scale", "<f4"), ("transformation", "<f4", 3), ("_padding", "<u4")]
 )
 
+# include/rt_abi.h rt_query_ray / rt_hit -- ray queries (rt_trace_rays, rt_pick): one ray (32 B,
+# two 16-B loads) and its closest-hit record (64 B, four 16-B stores)
+QUERY_RAY = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("_pad1", "<f4")])
+HIT = np.dtype(
+    [
+        ("t", "<f4"),
+        ("position", "<f4", 3),
+        ("normal", "<f4", 3),
+        ("u", "<f4"),
+        ("v", "<f4"),
+        ("material_index", "<u4"),
+        ("front_face", "<u4"),
+        ("kind", "<u4"),
+        ("index", "<u4"),
+        ("sub_object", "<u4"),
+        ("triangle", "<u4"),
+        ("_reserved", "<u4"),
+    ]
+)
+HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
+
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
+    (QUERY_RAY, 32), (HIT, 64),
 ):
     assert _dt.itemsize == _size, (_dt, _size)
 

@@ -52,6 +52,12 @@ hipError_t rt_launch_brute_wf(const KernelArgs& ka, bool tris, bool scalar_strea
                               hipStream_t stream);
 size_t rt_brute_wf_tile_bytes(bool scalar_stream);
 uint32_t rt_brute_wf_chunk();
+uint32_t rt_query_threads(int mode);
+hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+                           const void* rays, void* hits, uint64_t count, unsigned long long* counter,
+                           uint32_t wave_chunk, hipStream_t stream);
+hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
 hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
                              uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
                              uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
@@ -72,6 +78,8 @@ static_assert(sizeof(rt_scene_triangle) == 112, "SceneTriangle is 112 bytes");
 static_assert(sizeof(rt_scene_material) == 32, "SceneMaterial is 32 bytes");
 static_assert(sizeof(rt_object_info) == 48, "ObjectInfo is 48 bytes");
 static_assert(sizeof(rt_sub_object_info) == 32, "SubObjectInfo is 32 bytes");
+static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
+static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
 static_assert(sizeof(rt_sub_object_info) == sizeof(RtSubObject), "sub-object record");
@@ -136,6 +144,13 @@ constexpr uint32_t kMaxFrameBatch = 64;
 // in order afterwards) up to this many frames x samples; larger batches run each
 // pixel's frames back to back on one lane.
 constexpr uint32_t kMaxParallelLights = 64;
+// Ray queries (query.hip). rt_trace_rays stages its rays and records through pinned memory in
+// chunks of this many rays (96 B each: 6 MiB pinned, 6 MiB of device scratch); tuning "query_chunk".
+constexpr uint32_t kDefaultQueryChunk = 65536;
+constexpr uint32_t kMaxQueryChunk = 1u << 24;
+// A query of fewer rays than this launches the mode-0 instance (the scene read from global
+// memory) instead of staging the LDS image in every workgroup: measured crossover, DESIGN.md §5.4b.
+constexpr uint64_t kQueryStageMinRays = 262144;
 
 }  // namespace
 
@@ -359,6 +374,19 @@ struct rt_ctx {
     double resolve_total_ms = 0.0;  // rt_resolve_frames_kernel spans of the timed batches
     uint64_t n_resolve_timed = 0;
     float last_ms = 0.0f;
+
+    // ray queries (rt_trace_rays, rt_trace_rays_device, rt_pick; query.hip)
+    uint32_t query_chunk = kDefaultQueryChunk;  // tuning "query_chunk": rays per staged chunk of rt_trace_rays
+    int query_lds_mode = -1;                    // tuning "query_lds_mode": -1 by batch size, else the highest placement
+    unsigned long long* d_query_next = nullptr; // the kernel's chunk counter
+    void* d_query_buf = nullptr;                // rt_trace_rays / rt_pick scratch: rays, then records
+    size_t query_buf_rays = 0, query_buf_bytes = 0;
+    void* query_pinned = nullptr;               // the same on the host, pinned
+    size_t query_pinned_rays = 0;
+    int q_occ_mode = -1;                        // occupancy of the last query instance
+    bool q_occ_tris = false;
+    size_t q_occ_lds = 0;
+    int q_occ_blocks = 0;
 
     std::string err;
 };
@@ -826,10 +854,12 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_tile_sched[0], ctx->d_tile_sched[1], ctx->d_frame_light[0], ctx->d_frame_light[1],
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
-                    ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts};
+                    ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
+                    ctx->d_query_next, ctx->d_query_buf};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->query_pinned) (void)hipHostFree(ctx->query_pinned);
     for (hipEvent_t ev : {ctx->staging_done, ctx->ev_resolved[0], ctx->ev_resolved[1], ctx->ev_aux_done,
                           ctx->ev_primary})
         if (ev) (void)hipEventDestroy(ev);
@@ -1065,22 +1095,27 @@ static int dispatch_frames(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     return rc;
 }
 
-// One launch rendering `frames` frames starting at Params.accumulation_index.
-static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
+// ---- the scene as a launch sees it ------------------------------------------------------------
+//
+// The scene-view part of the kernel arguments, shared by the frame launches (dispatch_batch) and
+// the ray queries (run_query): the scene and camera fields, the LDS carve-up with the placement
+// mode it allows (0: everything read from global memory, 1: spheres / materials / objects / sphere
+// BVH staged in LDS, 2: also the triangle accelerator), and what the accelerators' walks read in
+// that mode (direction-ordered and quantized nodes, leaf certificates, leaf triangle blocks),
+// derived on the device when stale.
+struct SceneLaunch {
+    bool tris = false;      // the scene has objects: else the sphere-only kernels
+    int mode = 0;           // LDS placement mode
+    uint32_t layouts = 1;   // sphere BVH layouts staged (1 or 8)
+    size_t mode1_bytes = 0, mode2_bytes = 0;  // the LDS images of modes 1 and 2, tail included
+    size_t lds_bytes = 0;   // the image of `mode`
+    bool coop = false;      // cooperative leaf batches: per-wave LDS scratch after the image
+};
+
+static size_t al16(size_t x) { return (x + 15) & ~size_t(15); }
+
+static void scene_base_args(rt_ctx* ctx, KernelArgs& ka) {
     const rt_params& p = ctx->params;
-    {
-        int rc = refresh_sphere_slots(ctx, p.sphere_count, p.object_count == 0);
-        if (rc) return rc;
-        rc = refresh_tri_accel(ctx, p.object_count);
-        if (rc) return rc;
-    }
-    KernelArgs ka{};
-    ka.camera_rays = ctx->d_rays;
-    ka.accum = ctx->d_accum;
-    ka.output = ctx->d_out;
-    ka.ray_counter = ctx->d_counter;
-    ka.diag = ctx->d_counter + 1;
-    ka.queue_stripes = ctx->queue_stripes;  // (queue counters: per stream, set at launch)
     ka.sphere_slots = ctx->d_slot_sph;
     ka.sphere_orig = ctx->d_slot_orig;
     ka.sphere_material = ctx->d_sph_mat;
@@ -1131,6 +1166,196 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     ka.aspect = (float)ctx->width / (float)ctx->height;  // src/camera.rs:142
     std::memcpy(ka.inv_proj, ctx->inv_proj, sizeof(ka.inv_proj));
     std::memcpy(ka.inv_view, ctx->inv_view, sizeof(ka.inv_view));
+}
+
+// Lays out the LDS image for `layouts` sphere BVH layouts and returns the highest placement mode
+// up to `max_mode` that it fits.
+// dynamic LDS carve-up: sphere slots | materials | objects | slot->orig | sphere materials | BVH | srgb
+static int scene_carve_layouts(rt_ctx* ctx, KernelArgs& ka, uint32_t layouts, size_t mode1_budget, int max_mode,
+                               SceneLaunch& sl) {
+    const rt_params& p = ctx->params;
+    size_t off = al16((size_t)ctx->n_slots * 16);
+    ka.lds_mat_offset = (uint32_t)off;
+    off = al16(off + (size_t)ctx->n_mat_dev * sizeof(RtMaterial));
+    ka.lds_mat_aux_offset = (uint32_t)off;
+    off = al16(off + (size_t)ctx->n_mat_dev * 32);
+    ka.lds_obj_offset = (uint32_t)off;
+    off = al16(off + (size_t)p.object_count * sizeof(RtObject));
+    ka.lds_orig_offset = (uint32_t)off;
+    off = al16(off + (size_t)ctx->n_slots * 4);
+    ka.lds_smat_offset = (uint32_t)off;
+    off = al16(off + (size_t)p.sphere_count * 4);
+    ka.lds_nodes_offset = (uint32_t)off;
+    off = al16(off + (size_t)layouts * ctx->n_nodes * sizeof(SphereBvhNode));
+    sl.mode1_bytes = off + kLdsTailBytes;
+    ka.lds_tri_nodes_offset = (uint32_t)off;
+    off = al16(off + (size_t)ka.tri_nodes * sizeof(SphereBvhNode));
+    ka.lds_tri_prims_offset = (uint32_t)off;
+    off = al16(off + (size_t)ka.tri_prim_count * sizeof(SubObjectPrim));
+    // the sub-object records the leaves read, when they fit the mode-2 budget too
+    // (one dependent global load less per leaf test; tuning "stage_subs" 0 switches it off)
+    ka.lds_sub_offset = 0;
+    if (ctx->stage_subs && ka.sub_object_count != 0) {
+        const size_t with = al16(off + (size_t)ka.sub_object_count * sizeof(RtSubObject));
+        if (with + kLdsTailBytes <= kLdsAccelBudget) {
+            ka.lds_sub_offset = (uint32_t)off;
+            off = with;
+        }
+    }
+    sl.mode2_bytes = off + kLdsTailBytes;
+    if (ka.tri_accel && ka.tri_nodes != 0 && sl.mode2_bytes <= kLdsAccelBudget && max_mode >= 2)
+        return 2;
+    if (sl.mode1_bytes <= mode1_budget && max_mode >= 1) return 1;
+    return 0;
+}
+
+// Direction-ordered sphere BVH layouts (order_bvh_by_octant) when all eight
+// fit the LDS mode that one layout gets (up to the mode-2 budget, in fewer,
+// larger workgroups); otherwise layout 0 alone.
+static void scene_carve(rt_ctx* ctx, KernelArgs& ka, int max_mode, SceneLaunch& sl) {
+    sl.tris = ctx->params.object_count != 0;
+    sl.mode = scene_carve_layouts(ctx, ka, 1, kLdsSceneBudget, max_mode, sl);
+    sl.layouts = 1;
+    if (ctx->sphere_octants && ctx->n_nodes != 0) {
+        if (scene_carve_layouts(ctx, ka, 8, kLdsAccelBudget, max_mode, sl) == sl.mode)
+            sl.layouts = 8;
+        else
+            scene_carve_layouts(ctx, ka, 1, kLdsSceneBudget, max_mode, sl);
+    }
+}
+
+// What the walks of placement sl.mode read, derived when stale (primary stream), the walk's batch
+// thresholds, and the image size.
+static int scene_accel_args(rt_ctx* ctx, KernelArgs& ka, SceneLaunch& sl) {
+    ka.sphere_nodes = sl.layouts * ctx->n_nodes;
+    ka.sphere_octant_stride = sl.layouts == 8 ? ctx->n_nodes : 0u;
+    ka.sphere_boxes_ordered = (sl.layouts == 8 && ctx->sphere_boxes_ordered && !sl.tris) ? 1u : 0u;
+    const bool certified = sl.tris && sl.mode <= 1 && ka.tri_accel && ctx->tri_prune_mode == 1;
+    ka.trav_threshold = ctx->trav_threshold ? ctx->trav_threshold : trav_threshold_for(sl.mode, sl.tris, certified);
+    ka.leaf_batch = ctx->leaf_batch ? ctx->leaf_batch : leaf_batch_for(sl.mode, certified);
+    // walks of the binary triangle accelerator from global memory read its direction-ordered
+    // layouts (8 x tri_nodes positions, 32-B and 16-B quantized copies), else the single one
+    ka.tri_qnodes = nullptr;
+    ka.tri_qgrid = nullptr;
+    ka.tri_octant_stride = 0;
+    const bool global_walk = sl.tris && sl.mode <= 1 && ka.tri_accel && ka.tri_nodes != 0;
+    const bool octants = global_walk && ctx->tri_octants_built;
+    const bool qnodes = global_walk && ctx->use_qnodes;
+    if (octants || qnodes) {
+        const uint32_t n_out = octants ? 8u * ka.tri_nodes : ka.tri_nodes;
+        if (qnodes && ctx->qnodes_cap < n_out) {
+            RT_HIP(ctx, join_aux(ctx));
+            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_tri_qnodes) RT_HIP(ctx, hipFree(ctx->d_tri_qnodes));
+            ctx->d_tri_qnodes = nullptr;
+            ctx->qnodes_cap = 0;
+            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qnodes), (size_t)n_out * sizeof(uint4)));
+            ctx->qnodes_cap = n_out;
+            ctx->qnodes_dirty = true;
+        }
+        if (!ctx->d_tri_qgrid) RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qgrid), 2 * sizeof(float4)));
+        if (ctx->qnodes_dirty || ctx->derived_octants != octants || ctx->derived_qnodes != qnodes) {
+            // after the accelerator's upload or refit (primary stream)
+            RT_HIP(ctx, rt_launch_quantize_tri_nodes(reinterpret_cast<const SphereBvhNode*>(ctx->d_tri_bvh),
+                                                     ka.tri_nodes, octants ? ctx->d_tri_src8 : nullptr,
+                                                     octants ? ctx->d_tri_skip8 : nullptr, n_out,
+                                                     octants ? ctx->d_tri_bvh8 : nullptr,
+                                                     qnodes ? ctx->d_tri_qnodes : nullptr, ctx->d_tri_qgrid,
+                                                     ctx->stream));
+            ctx->qnodes_dirty = false;
+            ctx->derived_octants = octants;
+            ctx->derived_qnodes = qnodes;
+            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
+        }
+        if (qnodes) {
+            ka.tri_qnodes = ctx->d_tri_qnodes;
+            ka.tri_qgrid = ctx->d_tri_qgrid;
+        }
+        if (octants) {
+            ka.tri_bvh = reinterpret_cast<const float4*>(ctx->d_tri_bvh8);
+            ka.tri_octant_stride = ka.tri_nodes;
+            ka.tri_nodes = n_out;
+        }
+    }
+    // distance pruning of the binary walk (DESIGN.md §5.3c): certified (the leaf certificates,
+    // rebuilt on the device after any change), or the round-3 relative slack, or none
+    ka.tri_prune_mode = (sl.tris && ka.tri_accel && ka.tri_nodes != 0) ? (uint32_t)ctx->tri_prune_mode : 0u;
+    ka.tri_prune = ka.tri_prune_mode == 2u ? kTriPruneRho : 0.0f;
+    ka.tri_leafcert = nullptr;
+    if (ka.tri_prune_mode == 1u && ka.tri_prim_count != 0 && sl.mode <= 1) {  // (mode 2 culls by box alone)
+        const size_t bytes = (size_t)ka.tri_prim_count * sizeof(TriLeafCert);
+        if (ctx->tri_lcert_cap < bytes) {  // (re)allocate: nothing may still read them
+            RT_HIP(ctx, join_aux(ctx));
+            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_tri_lcert) RT_HIP(ctx, hipFree(ctx->d_tri_lcert));
+            ctx->d_tri_lcert = nullptr;
+            ctx->tri_lcert_cap = 0;
+            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_lcert), bytes));
+            ctx->tri_lcert_cap = bytes;
+            ctx->cones_dirty = true;
+        }
+        if (ctx->cones_dirty) {
+            RT_HIP(ctx, rt_launch_tri_leafcert(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_sub, ctx->d_tri,
+                                               ctx->n_tri_dev, ctx->d_tri_lcert, ctx->stream));
+            ctx->cones_dirty = false;
+            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
+        }
+        ka.tri_leafcert = ctx->d_tri_lcert;
+    }
+    // cooperative leaf batches (walks from global memory): the leaves' triangle blocks
+    ka.tri_leaftris = nullptr;
+    sl.coop = sl.tris && sl.mode <= 1 && ka.tri_accel && ka.tri_nodes != 0 && ka.tri_prim_count != 0 &&
+                      ctx->use_coop_leaves;
+    if (sl.coop) {
+        const size_t bytes = (size_t)ka.tri_prim_count * kLeafTriWords * sizeof(uint4);
+        if (ctx->tri_ltris_cap < bytes) {  // (re)allocate: nothing may still read them
+            RT_HIP(ctx, join_aux(ctx));
+            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (ctx->d_tri_ltris) RT_HIP(ctx, hipFree(ctx->d_tri_ltris));
+            ctx->d_tri_ltris = nullptr;
+            ctx->tri_ltris_cap = 0;
+            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_ltris), bytes));
+            ctx->tri_ltris_cap = bytes;
+            ctx->ltris_dirty = true;
+        }
+        if (ctx->ltris_dirty) {
+            RT_HIP(ctx, rt_launch_tri_leaftris(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_tri, ctx->n_tri_dev,
+                                               ctx->d_tri_ltris, ctx->stream));
+            ctx->ltris_dirty = false;
+            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
+        }
+        ka.tri_leaftris = ctx->d_tri_ltris;
+    }
+    if (sl.mode == 2) {
+        ka.lds_srgb_offset = (uint32_t)(sl.mode2_bytes - kLdsTailBytes);
+        sl.lds_bytes = sl.mode2_bytes;
+    } else if (sl.mode == 1) {
+        ka.lds_srgb_offset = (uint32_t)(sl.mode1_bytes - kLdsTailBytes);
+        sl.lds_bytes = sl.mode1_bytes;
+    } else {
+        ka.lds_srgb_offset = 0;
+        sl.lds_bytes = kLdsTailBytes;
+    }
+    return RT_OK;
+}
+
+// One launch rendering `frames` frames starting at Params.accumulation_index.
+static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
+    const rt_params& p = ctx->params;
+    {
+        int rc = refresh_sphere_slots(ctx, p.sphere_count, p.object_count == 0);
+        if (rc) return rc;
+        rc = refresh_tri_accel(ctx, p.object_count);
+        if (rc) return rc;
+    }
+    KernelArgs ka{};
+    ka.camera_rays = ctx->d_rays;
+    ka.accum = ctx->d_accum;
+    ka.output = ctx->d_out;
+    ka.ray_counter = ctx->d_counter;
+    ka.diag = ctx->d_counter + 1;
+    ka.queue_stripes = ctx->queue_stripes;  // (queue counters: per stream, set at launch)
+    scene_base_args(ctx, ka);
     ka.bounces = bounces;
     ka.tiles_x = ctx->tiles_x;
     ka.owned_tiles = ctx->owned_tiles;
@@ -1175,67 +1400,19 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
         ka.unit_tile_major = ctx->unit_tile_major ? 1u : 0u;
     }
 
-    // dynamic LDS carve-up: sphere slots | materials | objects | slot->orig | sphere materials | BVH | srgb
-    auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
-    const bool tris = p.object_count != 0;  // else the sphere-only kernels
-    size_t mode1_bytes = 0, mode2_bytes = 0;
-    // lays out the LDS image for `layouts` sphere BVH layouts and returns the LDS mode it fits
-    auto carve = [&](uint32_t layouts, size_t mode1_budget) -> int {
-        size_t off = al16((size_t)ctx->n_slots * 16);
-        ka.lds_mat_offset = (uint32_t)off;
-        off = al16(off + (size_t)ctx->n_mat_dev * sizeof(RtMaterial));
-        ka.lds_mat_aux_offset = (uint32_t)off;
-        off = al16(off + (size_t)ctx->n_mat_dev * 32);
-        ka.lds_obj_offset = (uint32_t)off;
-        off = al16(off + (size_t)p.object_count * sizeof(RtObject));
-        ka.lds_orig_offset = (uint32_t)off;
-        off = al16(off + (size_t)ctx->n_slots * 4);
-        ka.lds_smat_offset = (uint32_t)off;
-        off = al16(off + (size_t)p.sphere_count * 4);
-        ka.lds_nodes_offset = (uint32_t)off;
-        off = al16(off + (size_t)layouts * ctx->n_nodes * sizeof(SphereBvhNode));
-        mode1_bytes = off + kLdsTailBytes;
-        ka.lds_tri_nodes_offset = (uint32_t)off;
-        off = al16(off + (size_t)ka.tri_nodes * sizeof(SphereBvhNode));
-        ka.lds_tri_prims_offset = (uint32_t)off;
-        off = al16(off + (size_t)ka.tri_prim_count * sizeof(SubObjectPrim));
-        // the sub-object records the leaves read, when they fit the mode-2 budget too
-        // (one dependent global load less per leaf test; tuning "stage_subs" 0 switches it off)
-        ka.lds_sub_offset = 0;
-        if (ctx->stage_subs && ka.sub_object_count != 0) {
-            const size_t with = al16(off + (size_t)ka.sub_object_count * sizeof(RtSubObject));
-            if (with + kLdsTailBytes <= kLdsAccelBudget) {
-                ka.lds_sub_offset = (uint32_t)off;
-                off = with;
-            }
-        }
-        mode2_bytes = off + kLdsTailBytes;
-        if (ctx->force_global_scene) return 0;
-        if (ka.tri_accel && ka.tri_nodes != 0 && mode2_bytes <= kLdsAccelBudget && ctx->max_lds_mode >= 2)
-            return 2;
-        if (mode1_bytes <= mode1_budget && ctx->max_lds_mode >= 1) return 1;
-        return 0;
-    };
-    // Direction-ordered sphere BVH layouts (order_bvh_by_octant) when all eight
-    // fit the LDS mode that one layout gets (up to the mode-2 budget, in fewer,
-    // larger workgroups); otherwise layout 0 alone.
-    int mode = carve(1, kLdsSceneBudget);
-    uint32_t layouts = 1;
-    if (ctx->sphere_octants && ctx->n_nodes != 0) {
-        if (carve(8, kLdsAccelBudget) == mode)
-            layouts = 8;
-        else
-            carve(1, kLdsSceneBudget);
-    }
+    SceneLaunch sl;
+    scene_carve(ctx, ka, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
+    const bool tris = sl.tris;
+    const int mode = sl.mode;
     if (ctx->brute) {
         // the reference's sweeps as a wavefront (rt_brute_wf_kernel): the mode-1 scene image,
         // then the sub-object tiles (mode 1) or the hit lists (mode 2: the records through the
         // scalar cache; a scene without triangles has no records to stream and sweeps its
         // spheres in the LDS-tiled kernel); every pass (frame, sample) in order, one launch per
         // bounce level
-        carve(1, kLdsSceneBudget);
-        ka.lds_srgb_offset = (uint32_t)(mode1_bytes - kLdsTailBytes);
-        ka.lds_stack_offset = (uint32_t)al16(mode1_bytes);
+        scene_carve_layouts(ctx, ka, 1, kLdsSceneBudget, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
+        ka.lds_srgb_offset = (uint32_t)(sl.mode1_bytes - kLdsTailBytes);
+        ka.lds_stack_offset = (uint32_t)al16(sl.mode1_bytes);
         const uint32_t samples = ka.accumulate == 1u ? ka.compute_per_frame : 1u;
         const uint64_t passes = (uint64_t)frames * samples;
         const bool scalar_stream = tris && ctx->brute == 2;
@@ -1298,116 +1475,13 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
         ctx->primary_dirty = true;
         return RT_OK;
     }
-    ka.sphere_nodes = layouts * ctx->n_nodes;
-    ka.sphere_octant_stride = layouts == 8 ? ctx->n_nodes : 0u;
-    ka.sphere_boxes_ordered = (layouts == 8 && ctx->sphere_boxes_ordered && !tris) ? 1u : 0u;
-    const bool certified = tris && mode <= 1 && ka.tri_accel && ctx->tri_prune_mode == 1;
-    ka.trav_threshold = ctx->trav_threshold ? ctx->trav_threshold : trav_threshold_for(mode, tris, certified);
-    ka.leaf_batch = ctx->leaf_batch ? ctx->leaf_batch : leaf_batch_for(mode, certified);
-    // walks of the binary triangle accelerator from global memory read its direction-ordered
-    // layouts (8 x tri_nodes positions, 32-B and 16-B quantized copies), else the single one
-    ka.tri_qnodes = nullptr;
-    ka.tri_qgrid = nullptr;
-    ka.tri_octant_stride = 0;
-    const bool global_walk = tris && mode <= 1 && ka.tri_accel && ka.tri_nodes != 0;
-    const bool octants = global_walk && ctx->tri_octants_built;
-    const bool qnodes = global_walk && ctx->use_qnodes;
-    if (octants || qnodes) {
-        const uint32_t n_out = octants ? 8u * ka.tri_nodes : ka.tri_nodes;
-        if (qnodes && ctx->qnodes_cap < n_out) {
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_qnodes) RT_HIP(ctx, hipFree(ctx->d_tri_qnodes));
-            ctx->d_tri_qnodes = nullptr;
-            ctx->qnodes_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qnodes), (size_t)n_out * sizeof(uint4)));
-            ctx->qnodes_cap = n_out;
-            ctx->qnodes_dirty = true;
-        }
-        if (!ctx->d_tri_qgrid) RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qgrid), 2 * sizeof(float4)));
-        if (ctx->qnodes_dirty || ctx->derived_octants != octants || ctx->derived_qnodes != qnodes) {
-            // after the accelerator's upload or refit (primary stream)
-            RT_HIP(ctx, rt_launch_quantize_tri_nodes(reinterpret_cast<const SphereBvhNode*>(ctx->d_tri_bvh),
-                                                     ka.tri_nodes, octants ? ctx->d_tri_src8 : nullptr,
-                                                     octants ? ctx->d_tri_skip8 : nullptr, n_out,
-                                                     octants ? ctx->d_tri_bvh8 : nullptr,
-                                                     qnodes ? ctx->d_tri_qnodes : nullptr, ctx->d_tri_qgrid,
-                                                     ctx->stream));
-            ctx->qnodes_dirty = false;
-            ctx->derived_octants = octants;
-            ctx->derived_qnodes = qnodes;
-            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
-        }
-        if (qnodes) {
-            ka.tri_qnodes = ctx->d_tri_qnodes;
-            ka.tri_qgrid = ctx->d_tri_qgrid;
-        }
-        if (octants) {
-            ka.tri_bvh = reinterpret_cast<const float4*>(ctx->d_tri_bvh8);
-            ka.tri_octant_stride = ka.tri_nodes;
-            ka.tri_nodes = n_out;
-        }
+    {
+        const int rc = scene_accel_args(ctx, ka, sl);
+        if (rc) return rc;
     }
-    // distance pruning of the binary walk (DESIGN.md §5.3c): certified (the leaf certificates,
-    // rebuilt on the device after any change), or the round-3 relative slack, or none
-    ka.tri_prune_mode = (tris && ka.tri_accel && ka.tri_nodes != 0) ? (uint32_t)ctx->tri_prune_mode : 0u;
-    ka.tri_prune = ka.tri_prune_mode == 2u ? kTriPruneRho : 0.0f;
-    ka.tri_leafcert = nullptr;
-    if (ka.tri_prune_mode == 1u && ka.tri_prim_count != 0 && mode <= 1) {  // (mode 2 culls by box alone)
-        const size_t bytes = (size_t)ka.tri_prim_count * sizeof(TriLeafCert);
-        if (ctx->tri_lcert_cap < bytes) {  // (re)allocate: nothing may still read them
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_lcert) RT_HIP(ctx, hipFree(ctx->d_tri_lcert));
-            ctx->d_tri_lcert = nullptr;
-            ctx->tri_lcert_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_lcert), bytes));
-            ctx->tri_lcert_cap = bytes;
-            ctx->cones_dirty = true;
-        }
-        if (ctx->cones_dirty) {
-            RT_HIP(ctx, rt_launch_tri_leafcert(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_sub, ctx->d_tri,
-                                               ctx->n_tri_dev, ctx->d_tri_lcert, ctx->stream));
-            ctx->cones_dirty = false;
-            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
-        }
-        ka.tri_leafcert = ctx->d_tri_lcert;
-    }
-    // cooperative leaf batches (walks from global memory): the leaves' triangle blocks
-    ka.tri_leaftris = nullptr;
-    const bool coop = tris && mode <= 1 && ka.tri_accel && ka.tri_nodes != 0 && ka.tri_prim_count != 0 &&
-                      ctx->use_coop_leaves;
-    if (coop) {
-        const size_t bytes = (size_t)ka.tri_prim_count * kLeafTriWords * sizeof(uint4);
-        if (ctx->tri_ltris_cap < bytes) {  // (re)allocate: nothing may still read them
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_ltris) RT_HIP(ctx, hipFree(ctx->d_tri_ltris));
-            ctx->d_tri_ltris = nullptr;
-            ctx->tri_ltris_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_ltris), bytes));
-            ctx->tri_ltris_cap = bytes;
-            ctx->ltris_dirty = true;
-        }
-        if (ctx->ltris_dirty) {
-            RT_HIP(ctx, rt_launch_tri_leaftris(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_tri, ctx->n_tri_dev,
-                                               ctx->d_tri_ltris, ctx->stream));
-            ctx->ltris_dirty = false;
-            ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
-        }
-        ka.tri_leaftris = ctx->d_tri_ltris;
-    }
-    size_t lds_bytes;
-    if (mode == 2) {
-        ka.lds_srgb_offset = (uint32_t)(mode2_bytes - kLdsTailBytes);
-        lds_bytes = mode2_bytes;
-    } else if (mode == 1) {
-        ka.lds_srgb_offset = (uint32_t)(mode1_bytes - kLdsTailBytes);
-        lds_bytes = mode1_bytes;
-    } else {
-        ka.lds_srgb_offset = 0;
-        lds_bytes = kLdsTailBytes;
-    }
+    const bool coop = sl.coop;
+    const size_t mode1_bytes = sl.mode1_bytes, mode2_bytes = sl.mode2_bytes;
+    size_t lds_bytes = sl.lds_bytes;
     // per-thread LDS after the scene image: the cooperative leaf batch's per-wave scratch
     const size_t lane_pt = coop ? (size_t)kLeafBatchWaveBytes / 64u : 0u;
     // Persistent grid: as many workgroups as can be resident (never more than
@@ -1652,6 +1726,175 @@ int rt_copy_output_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_r
         return fail(ctx, RT_E_INVALID, "rt_copy_output_to_device: bytes_per_row < 4 * width");
     RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_out, 4u * (size_t)ctx->width,
                                  4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+// ---- ray queries (query.hip) -------------------------------------------------------------------
+//
+// A query reads the scene and writes the caller's records, nothing else: the queued frames stay
+// queued (nothing changed the scene since they were queued -- every update launches them first --
+// so they render the same bits before or after the query), and the accumulation, the output, the
+// counters, the timing totals and the tile schedule are not touched. The accelerators are
+// prepared exactly as a frame launch prepares them (the same refresh and derivation, whichever
+// comes first does the work), on the primary stream after everything the auxiliary stream runs.
+static int query_enter(rt_ctx* ctx) {
+    RT_HIP(ctx, join_aux(ctx));
+    if (!ctx->d_query_next) {
+        const int rc = dev_alloc(ctx, &ctx->d_query_next, 1);
+        if (rc) return rc;
+    }
+    const rt_params& p = ctx->params;
+    int rc = refresh_sphere_slots(ctx, p.sphere_count, p.object_count == 0);
+    if (rc) return rc;
+    return refresh_tri_accel(ctx, p.object_count);
+}
+
+// The scene view of a query of `count` rays: the frame launches' carve, with the placement capped
+// by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
+static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, SceneLaunch& sl, size_t* lds_bytes,
+                       int* blocks_per_cu) {
+    scene_base_args(ctx, ka);
+    ka.camera_rays = ctx->d_rays;
+    int max_mode = ctx->force_global_scene ? 0 : ctx->max_lds_mode;
+    if (ctx->query_lds_mode >= 0)
+        max_mode = ctx->query_lds_mode;
+    else if (count < kQueryStageMinRays)
+        max_mode = 0;
+    for (;; --max_mode) {
+        // (the carve reads ka.tri_nodes of the single layout: scene_accel_args may have scaled it)
+        ka.tri_nodes = ka.tri_accel ? ctx->tri_nodes : 0u;
+        ka.tri_bvh = reinterpret_cast<const float4*>(ctx->d_tri_bvh);
+        scene_carve(ctx, ka, max_mode, sl);
+        const int rc = scene_accel_args(ctx, ka, sl);
+        if (rc) return rc;
+        const uint32_t threads = rt_query_threads(sl.mode);
+        ka.lds_leafbatch_offset = (uint32_t)al16(sl.lds_bytes);
+        *lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
+        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_tris != sl.tris ||
+            ctx->q_occ_lds != *lds_bytes) {
+            int n = 0;
+            const hipError_t e = rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
+            if (e != hipSuccess) (void)hipGetLastError();
+            ctx->q_occ_mode = sl.mode;
+            ctx->q_occ_tris = sl.tris;
+            ctx->q_occ_lds = *lds_bytes;
+            ctx->q_occ_blocks = e == hipSuccess ? n : 0;
+        }
+        if (ctx->q_occ_blocks > 0) break;
+        // an image this instance cannot take: the next lower placement (mode 0 fits every scene)
+        if (sl.mode == 0) return fail(ctx, RT_E_HIP, "ray query: the kernel does not fit the device");
+        max_mode = sl.mode;
+    }
+    *blocks_per_cu = ctx->q_occ_blocks;
+    return RT_OK;
+}
+
+// Traces `count` rays at device pointer `rays` into `hits`, stream-ordered on the primary stream.
+static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count) {
+    if (count == 0) return RT_OK;
+    KernelArgs ka{};
+    SceneLaunch sl;
+    size_t lds_bytes = 0;
+    int per_cu = 0;
+    const int rc = query_scene(ctx, ka, count, sl, &lds_bytes, &per_cu);
+    if (rc) return rc;
+    const uint32_t waves_per_block = rt_query_threads(sl.mode) / 64u;
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
+    const uint64_t wanted = (count + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
+    // rays per claim: about two claims per wave, whole waves of rays, at most 256
+    const uint64_t per_wave = count / ((uint64_t)blocks * waves_per_block * 2u);
+    const uint32_t wave_chunk = (uint32_t)std::min<uint64_t>(256u, std::max<uint64_t>(64u, (per_wave + 63u) & ~63ull));
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    const hipError_t e = rt_launch_query(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, hits, count, ctx->d_query_next,
+                                         wave_chunk, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_query_kernel launch", e);
+    return RT_OK;
+}
+
+// The staging of rt_trace_rays and rt_pick: `n` rays then `n` records, on the device and pinned.
+static int query_buffers(rt_ctx* ctx, size_t n) {
+    if (ctx->query_buf_rays < n) {
+        const int rc = grow_buffer(ctx, &ctx->d_query_buf, &ctx->query_buf_bytes, n * (sizeof(rt_query_ray) + sizeof(rt_hit)));
+        if (rc) return rc;
+        ctx->query_buf_rays = n;
+    }
+    if (ctx->query_pinned_rays < n) {
+        if (ctx->query_pinned) RT_HIP(ctx, hipHostFree(ctx->query_pinned));
+        ctx->query_pinned = nullptr;
+        ctx->query_pinned_rays = 0;
+        RT_HIP(ctx, hipHostMalloc(&ctx->query_pinned, n * (sizeof(rt_query_ray) + sizeof(rt_hit)), hipHostMallocDefault));
+        ctx->query_pinned_rays = n;
+    }
+    return RT_OK;
+}
+
+int rt_trace_rays_device(rt_ctx* ctx, const void* rays_device, void* hits_device, uint64_t count) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    if (!rays_device || !hits_device) return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays or hits is NULL");
+    for (const void* ptr : {rays_device, (const void*)hits_device}) {
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays and hits must be device memory of the context's device");
+        }
+    }
+    if (((uintptr_t)rays_device | (uintptr_t)hits_device) & 15u)
+        return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays and hits must be 16-byte aligned");
+    const int rc = query_enter(ctx);
+    if (rc) return rc;
+    return run_query(ctx, rays_device, hits_device, count);
+}
+
+int rt_trace_rays(rt_ctx* ctx, const rt_query_ray* rays, rt_hit* hits, uint64_t count) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    if (!rays || !hits) return fail(ctx, RT_E_INVALID, "rt_trace_rays: rays or hits is NULL");
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    const size_t cap = ctx->query_buf_rays;
+    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_hits = d_rays + cap * sizeof(rt_query_ray);
+    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
+    unsigned char* h_hits = h_rays + ctx->query_pinned_rays * sizeof(rt_query_ray);
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_rays, rays + done, n * sizeof(rt_query_ray));
+        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_query_ray), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run_query(ctx, d_rays, d_hits, n))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_hits, d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(hits + done, h_hits, n * sizeof(rt_hit));
+        done += n;
+    }
+    return RT_OK;
+}
+
+int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!hit) return fail(ctx, RT_E_INVALID, "rt_pick: hit is NULL");
+    if (x >= ctx->width || y >= ctx->height) return fail(ctx, RT_E_INVALID, "rt_pick: pixel outside the framebuffer");
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    if ((rc = query_buffers(ctx, 1))) return rc;
+    unsigned char* d_ray = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_hit = d_ray + ctx->query_buf_rays * sizeof(rt_query_ray);
+    {
+        // the pixel's un-jittered camera ray, as the kernels read or compute it (pixel_ray)
+        KernelArgs ka{};
+        scene_base_args(ctx, ka);
+        ka.camera_rays = ctx->d_rays;
+        RT_HIP(ctx, rt_launch_pick_ray(ka, x, y, d_ray, ctx->stream));
+    }
+    if ((rc = run_query(ctx, d_ray, d_hit, 1))) return rc;
+    unsigned char* h_hit = static_cast<unsigned char*>(ctx->query_pinned);
+    RT_HIP(ctx, hipMemcpyAsync(h_hit, d_hit, sizeof(rt_hit), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(hit, h_hit, sizeof(rt_hit));
     return RT_OK;
 }
 
@@ -1938,6 +2181,10 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         rc = flag(ctx->batch_schedule);
     } else if (k == "unit_tile_major") {
         rc = flag(ctx->unit_tile_major);
+    } else if (k == "query_chunk") {
+        if ((rc = range(1, (int32_t)kMaxQueryChunk)) == RT_OK) ctx->query_chunk = (uint32_t)v;
+    } else if (k == "query_lds_mode") {
+        if ((rc = range(-1, 2)) == RT_OK) ctx->query_lds_mode = v;
     } else if (k == "batch_memory_mb") {
         if ((rc = range(1, 1 << 30)) == RT_OK) ctx->batch_budget = (size_t)v << 20;
     } else {

@@ -349,7 +349,9 @@ __device__ __forceinline__ void tri_leaf(const SceneView& sv, const KernelArgs& 
 }
 
 // trace_ray's result (:342-353): the sphere wins only if strictly closer.
-template <bool kTris>
+// kAlwaysUv: the texture coordinates are computed whatever the texture size (ray queries return
+// them); by default they are skipped where no texel depends on them (1x1 layers, below).
+template <bool kTris, bool kAlwaysUv = false>
 __device__ __forceinline__ Hit trace_end(const SceneView& sv, const KernelArgs& ka, f3 o, f3 d, const TraceState& ts) {
     Hit h;
     h.t = kF32Max;
@@ -368,7 +370,7 @@ __device__ __forceinline__ Hit trace_end(const SceneView& sv, const KernelArgs& 
         h.p = o + d * ts.tri.t;
         // object_texture_coords, :568-578 (uv from the OBJECT bounds); unused
         // with 1x1 texture layers, as for spheres below
-        if (ka.tex_w != 1u || ka.tex_h != 1u) {
+        if (kAlwaysUv || ka.tex_w != 1u || ka.tex_h != 1u) {
             h.u = (h.p.x - ob.min_bounds[0]) / (ob.max_bounds[0] - ob.min_bounds[0]);
             h.v = (h.p.z - ob.min_bounds[2]) / (ob.max_bounds[2] - ob.min_bounds[2]);
         }
@@ -385,7 +387,7 @@ __device__ __forceinline__ Hit trace_end(const SceneView& sv, const KernelArgs& 
         // uv feeds only the texel fetch, and with 1x1 texture layers every uv
         // maps to texel (0, 0) (texel_coord clamps to [0, size-1]): the
         // acos/atan2 are then skipped (bit-identical; 4% of a C2 frame)
-        if (ka.tex_w != 1u || ka.tex_h != 1u) {
+        if (kAlwaysUv || ka.tex_w != 1u || ka.tex_h != 1u) {
             const float theta = acosf_c(-outward.y);
             const float phi = atan2f_c(-outward.z, outward.x) + kWgslPi;
             h.u = div_const(phi, kTwoPiWgsl, kInvTwoPiWgsl);  // exact: rt_math_selftest
@@ -396,6 +398,20 @@ __device__ __forceinline__ Hit trace_end(const SceneView& sv, const KernelArgs& 
         h.material_index = sv.sph_mat[ts.sph.orig];
     }
     return h;
+}
+
+// What trace_end's hit is, from the same state by the same rule (ray queries; shading does not
+// need it): kind 0 miss, 1 sphere, 2 triangle; the sphere's index as uploaded, or the object's;
+// the triangle's index in the triangle buffer (0 for spheres and misses).
+struct HitId {
+    uint32_t kind, index, triangle;
+};
+template <bool kTris>
+__device__ __forceinline__ HitId trace_end_id(const TraceState& ts) {
+    const float tt = (kTris && ts.tri.t != kF32Max) ? ts.tri.t : kF32Max;
+    if (ts.sph.t < tt) return HitId{1u, ts.sph.orig, 0u};
+    if (kTris && ts.tri.t != kF32Max) return HitId{2u, ts.tri.obj, ts.tri.tri};
+    return HitId{0u, 0u, 0u};
 }
 
 // sample_texture, compute_shader.wgsl:26-32: the raw RGBA8 texel (decoded later).

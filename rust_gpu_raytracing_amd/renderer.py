@@ -268,6 +268,61 @@ class Renderer:
         self._call("rt_read_accumulation", N.ptr(out))
         return out
 
+    # ------------------------------------------------------------------ ray queries
+    def trace_rays(self, rays):
+        """The closest hit of every ray (rt_trace_rays): bit-identical to the reference's
+        trace_ray, against the scene as it is now, without touching anything a render reads.
+
+        ``rays``: an (n, 6) float32 array (origin, direction) or a ``buffers.QUERY_RAY`` array;
+        returns a ``buffers.HIT`` array. A CUDA torch tensor of shape (n, 8) float32
+        (rt_query_ray records) goes through rt_trace_rays_device instead -- no host round
+        trip, stream-ordered on the context's stream -- and returns a CUDA (n, 16) int32
+        tensor of rt_hit records."""
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            return self._trace_rays_device(rays)
+        rays = np.asarray(rays)
+        if rays.dtype != B.QUERY_RAY:
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 6:
+                raise ValueError("rays must be (n, 6) float32 or a QUERY_RAY array")
+            rays = np.zeros(r.shape[0], B.QUERY_RAY)
+            rays["origin"] = r[:, :3]
+            rays["direction"] = r[:, 3:]
+        rays = np.ascontiguousarray(rays.reshape(-1))
+        hits = np.zeros(rays.shape[0], B.HIT)
+        self._call("rt_trace_rays", N.ptr(rays), N.ptr(hits), rays.shape[0])
+        return hits
+
+    def _trace_rays_device(self, rays):
+        import torch
+
+        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
+        if rays.device.index != self.device:
+            raise ValueError("device rays must live on the renderer's device")
+        rays = rays.contiguous()
+        hits = torch.empty((rays.shape[0], 16), dtype=torch.int32, device=rays.device)
+        if rays.shape[0] == 0:
+            return hits
+        # the query runs on the context's stream: order it after the tensor's producers,
+        # and the caller's stream after it
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
+        cur = torch.cuda.current_stream(rays.device)
+        mine.wait_stream(cur)
+        self._call("rt_trace_rays_device", ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(hits.data_ptr()),
+                   rays.shape[0])
+        # (no record_stream on the context's stream: the caller's stream, which owns both tensors,
+        # is ordered after the query here, and the context's stream may be destroyed -- close() --
+        # before the tensors are freed)
+        cur.wait_stream(mine)
+        return hits
+
+    def pick(self, x: int, y: int) -> np.ndarray:
+        """The closest hit of pixel (x, y)'s un-jittered camera ray (rt_pick): one ``buffers.HIT``."""
+        hit = np.zeros(1, B.HIT)
+        self._call("rt_pick", int(x), int(y), N.ptr(hit))
+        return hit[0]
+
     def update_texture(self, alignment: int = 256) -> np.ndarray:
         """``Renderer::update_texture`` (src/renderer.rs:254-283), headless: the
         packed output as the Rgba8Unorm display texture the reference copies it
