@@ -45,7 +45,8 @@ extern "C" {
 
 /* History: ... 11 (device display copy, default frame batch), 12 (tuning keys instead of
  * environment variables); 12, additive: ray queries (rt_trace_rays, rt_trace_rays_device,
- * rt_pick, rt_query_ray, rt_hit -- nothing earlier changed, so the number stays). */
+ * rt_pick, rt_query_ray, rt_hit -- nothing earlier changed, so the number stays); 12,
+ * additive: occlusion queries (rt_occluded, rt_occluded_device, rt_occlusion_ray). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -354,6 +355,68 @@ RT_API int rt_trace_rays_device(rt_ctx* ctx, const void* rays_device, void* hits
  * is outside the framebuffer. Synchronous. */
 RT_API int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit);
 
+/* ---- occlusion queries (ABI 12, additive: occlusion queries) ---------------
+ *
+ * "Is anything in the way before t_max?" for arbitrary rays: shadow rays, line of sight,
+ * occlusion baking. An any-hit search: it stops at the first primitive that decides the
+ * answer and culls by t_max from the first node, which a closest-hit query cannot. */
+
+/* One ray with a distance bound. The layout of rt_query_ray with t_max in the place of
+ * _pad1, so one buffer can be handed to rt_trace_rays (which ignores the pad) and to
+ * rt_occluded. 32 bytes. */
+typedef struct rt_occlusion_ray {
+    float origin[3];
+    float _pad0;        /* ignored */
+    float direction[3]; /* need not be unit length */
+    float t_max;        /* in units of |direction|, like rt_hit.t */
+} rt_occlusion_ray;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_occlusion_ray) == 32, "rt_occlusion_ray is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_occlusion_ray) == 32, "rt_occlusion_ray is 32 bytes");
+#endif
+
+/* Writes one byte per ray, in order, exactly 0 or 1; no byte outside [0, count) is written.
+ *
+ * A ray is occluded (1) if and only if at least one primitive, tested on its own by the
+ * reference's test, is accepted at a distance t with t < t_max in f32: the sphere test of
+ * check_spheres (compute_shader.wgsl:355-404: disc >= 0, t > 0) or the triangle test of
+ * check_triangles (:422-517, behind its object and sub-object ray_in_bounds: dist >= 0,
+ * u, v, w >= 0). The answer does not depend on the order primitives are visited in and
+ * no NaN takes part in it. Consequences:
+ *  - For every ray whose closest-hit search meets no NaN distance, the byte equals
+ *    `hit.kind != RT_HIT_MISS && hit.t < t_max` on the record rt_trace_rays returns for
+ *    that ray. The comparison is strict: t_max == hit.t is NOT occluded.
+ *  - t_max = +inf or 3.4028235e38f asks "is there any hit at all" (a hit as rt_trace_rays
+ *    defines one: t < 3.4028235e38f). A miss is not occluded for any t_max.
+ *  - t_max <= 0 or NaN gives 0.
+ *  - A candidate whose distance is NaN never occludes: the measure-zero case of a ray lying
+ *    exactly in a triangle's plane, which the reference's sweep accepts (:457). This is the
+ *    one difference from the closest-hit record, whose t can be NaN there and then hides a
+ *    sphere that does block the ray.
+ *  - Exactness holds for the domain of the ray queries above: finite components,
+ *    |direction| in [1e-5, 1e5], |origin| <= 1e15. Outside it the byte is unspecified; the
+ *    search still terminates.
+ *
+ * Scene visibility and side effects are those of rt_trace_rays: the query sees the scene as
+ * of the call, with the accelerators prepared exactly as a dispatch prepares them, and
+ * changes nothing a render can observe (queued frames stay queued; the accumulation index,
+ * rt_ray_count, the timing totals and the tile schedule are untouched). The bytes do not
+ * depend on the brute-force mode, on any rt_set_tuning key or on triangle pruning modes 0
+ * and 1 (mode 2 is inexact here as for frames and ray queries).
+ *
+ * rt_occluded: host pointers, synchronous. Staged through the pinned buffer of
+ * rt_trace_rays in chunks of tuning "query_chunk" rays (32 bytes in, 1 byte out per ray).
+ * rt_occluded_device: device pointers on the context's device; the rays 16-byte aligned,
+ * the result at any alignment; stream-ordered on rt_stream(ctx), no host copy,
+ * asynchronous. RT_E_INVALID when either is not device memory of the context's device.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries.
+ * count == 0 returns RT_OK and launches nothing; NULL pointers with count > 0 are
+ * RT_E_INVALID. */
+RT_API int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count);
+RT_API int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count);
+
 /* Readback (new: the reference only blits output_data to the swapchain,
  * src/renderer.rs:254-283). Synchronous; whole framebuffer, row-major
  * width*height. Pixels of tiles owned by another rank are left as they were
@@ -443,9 +506,9 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "tri_octants" 1|0, "tri_qnodes" 1|0, "coop_leaves" 1|0, "stage_subs" 1|0,
  *   "primary_pass" -1|0|1 (-1: by scene), "primary_threads" 256|64|128|512|1024,
  *   "primary_waves" 8|0, "primary_tile_major" 1|0;
- *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays),
+ *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays and rt_occluded),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
- *   0..2: the highest LDS staging mode of the query kernel, falling back as a dispatch does).
+ *   0..2: the highest LDS staging mode of the query and occlusion kernels, falling back as a dispatch does).
  * RT_E_INVALID for an unknown key or a value out of range. */
 RT_API int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value);
 

@@ -83,6 +83,11 @@ class rt_query_ray(ctypes.Structure):
                 ("direction", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
 
 
+class rt_occlusion_ray(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_float * 3), ("_pad0", ctypes.c_float),
+                ("direction", ctypes.c_float * 3), ("t_max", ctypes.c_float)]
+
+
 class rt_hit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
                 ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
@@ -92,6 +97,7 @@ class rt_hit(ctypes.Structure):
 
 assert ctypes.sizeof(rt_params) == 48
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
+assert ctypes.sizeof(rt_occlusion_ray) == 32
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -129,6 +135,8 @@ SIGNATURES = {
     "rt_trace_rays": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_trace_rays_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_pick": (ctypes.c_int, [_P, _U32, _U32, _P]),
+    "rt_occluded": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_occluded_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_read_output_pitched": (ctypes.c_int, [_P, _P, _U32]),
     "rt_bytes_per_row": (_U32, [_U32, _U32]),
     "rt_ray_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),

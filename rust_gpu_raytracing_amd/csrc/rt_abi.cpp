@@ -57,6 +57,11 @@ hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks
 hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
                            const void* rays, void* hits, uint64_t count, unsigned long long* counter,
                            uint32_t wave_chunk, hipStream_t stream);
+uint32_t rt_occlusion_threads(int mode);
+hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+                               const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
+                               uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
 hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
                              uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
@@ -80,6 +85,7 @@ static_assert(sizeof(rt_object_info) == 48, "ObjectInfo is 48 bytes");
 static_assert(sizeof(rt_sub_object_info) == 32, "SubObjectInfo is 32 bytes");
 static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
+static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
 static_assert(sizeof(rt_sub_object_info) == sizeof(RtSubObject), "sub-object record");
@@ -384,6 +390,7 @@ struct rt_ctx {
     void* query_pinned = nullptr;               // the same on the host, pinned
     size_t query_pinned_rays = 0;
     int q_occ_mode = -1;                        // occupancy of the last query instance
+    bool q_occ_any_hit = false;                 // (of rt_occlusion_kernel, else rt_query_kernel)
     bool q_occ_tris = false;
     size_t q_occ_lds = 0;
     int q_occ_blocks = 0;
@@ -1751,7 +1758,8 @@ static int query_enter(rt_ctx* ctx) {
 
 // The scene view of a query of `count` rays: the frame launches' carve, with the placement capped
 // by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
-static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, SceneLaunch& sl, size_t* lds_bytes,
+// `any_hit`: for rt_occlusion_kernel (occlusion.hip), else rt_query_kernel.
+static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, bool any_hit, SceneLaunch& sl, size_t* lds_bytes,
                        int* blocks_per_cu) {
     scene_base_args(ctx, ka);
     ka.camera_rays = ctx->d_rays;
@@ -1767,15 +1775,17 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, SceneLaunch&
         scene_carve(ctx, ka, max_mode, sl);
         const int rc = scene_accel_args(ctx, ka, sl);
         if (rc) return rc;
-        const uint32_t threads = rt_query_threads(sl.mode);
+        const uint32_t threads = any_hit ? rt_occlusion_threads(sl.mode) : rt_query_threads(sl.mode);
         ka.lds_leafbatch_offset = (uint32_t)al16(sl.lds_bytes);
         *lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
-        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_tris != sl.tris ||
-            ctx->q_occ_lds != *lds_bytes) {
+        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_any_hit != any_hit ||
+            ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != *lds_bytes) {
             int n = 0;
-            const hipError_t e = rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
+            const hipError_t e = any_hit ? rt_occlusion_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
+                                         : rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
             if (e != hipSuccess) (void)hipGetLastError();
             ctx->q_occ_mode = sl.mode;
+            ctx->q_occ_any_hit = any_hit;
             ctx->q_occ_tris = sl.tris;
             ctx->q_occ_lds = *lds_bytes;
             ctx->q_occ_blocks = e == hipSuccess ? n : 0;
@@ -1789,16 +1799,17 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, SceneLaunch&
     return RT_OK;
 }
 
-// Traces `count` rays at device pointer `rays` into `hits`, stream-ordered on the primary stream.
-static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count) {
+// Traces `count` rays at device pointer `rays` into `hits`, stream-ordered on the primary stream:
+// rt_hit records, or with `any_hit` one occlusion byte per rt_occlusion_ray.
+static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count, bool any_hit = false) {
     if (count == 0) return RT_OK;
     KernelArgs ka{};
     SceneLaunch sl;
     size_t lds_bytes = 0;
     int per_cu = 0;
-    const int rc = query_scene(ctx, ka, count, sl, &lds_bytes, &per_cu);
+    const int rc = query_scene(ctx, ka, count, any_hit, sl, &lds_bytes, &per_cu);
     if (rc) return rc;
-    const uint32_t waves_per_block = rt_query_threads(sl.mode) / 64u;
+    const uint32_t waves_per_block = (any_hit ? rt_occlusion_threads(sl.mode) : rt_query_threads(sl.mode)) / 64u;
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
     const uint64_t wanted = (count + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
@@ -1806,6 +1817,22 @@ static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count) 
     const uint64_t per_wave = count / ((uint64_t)blocks * waves_per_block * 2u);
     const uint32_t wave_chunk = (uint32_t)std::min<uint64_t>(256u, std::max<uint64_t>(64u, (per_wave + 63u) & ~63ull));
     RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    if (any_hit) {
+        // Each wave's own first chunk: whole waves of consecutive rays, about half the wave's share,
+        // taken without a claim (the resident waves' first claims would queue at one counter
+        // address, about 20 ns each, while nothing else runs). The counter deals the other half,
+        // which evens out what the first chunks cost. A batch of at most one wave of rays per wave
+        // claims nothing.
+        const uint64_t waves = (uint64_t)blocks * waves_per_block;
+        const uint32_t first_chunk = (uint32_t)std::max<uint64_t>(64u, (count / waves / 2u) & ~63ull);
+        const uint64_t rest = count > waves * first_chunk ? count - waves * first_chunk : 0;
+        const uint32_t rest_chunk =
+            (uint32_t)std::min<uint64_t>(256u, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
+        const hipError_t e = rt_launch_occlusion(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, hits, count,
+                                                 ctx->d_query_next, rest_chunk, first_chunk, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, "rt_occlusion_kernel launch", e);
+        return RT_OK;
+    }
     const hipError_t e = rt_launch_query(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, hits, count, ctx->d_query_next,
                                          wave_chunk, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, "rt_query_kernel launch", e);
@@ -1895,6 +1922,56 @@ int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit) {
     RT_HIP(ctx, hipMemcpyAsync(h_hit, d_hit, sizeof(rt_hit), hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(hit, h_hit, sizeof(rt_hit));
+    return RT_OK;
+}
+
+// ---- occlusion queries (occlusion.hip) ---------------------------------------------------------
+//
+// The any-hit counterpart of the calls above, with the same scene visibility and the same absence
+// of side effects; rt_occluded stages through the same buffers (32 B in, 1 B out per ray: the
+// bytes go where the records of a closest-hit chunk would).
+int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    if (!rays_device || !occluded_device)
+        return fail(ctx, RT_E_INVALID, "rt_occluded_device: rays or occluded is NULL");
+    for (const void* ptr : {rays_device, (const void*)occluded_device}) {
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID,
+                        "rt_occluded_device: rays and occluded must be device memory of the context's device");
+        }
+    }
+    if ((uintptr_t)rays_device & 15u) return fail(ctx, RT_E_INVALID, "rt_occluded_device: rays must be 16-byte aligned");
+    const int rc = query_enter(ctx);
+    if (rc) return rc;
+    return run_query(ctx, rays_device, occluded_device, count, true);
+}
+
+int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    if (!rays || !occluded) return fail(ctx, RT_E_INVALID, "rt_occluded: rays or occluded is NULL");
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_occ = d_rays + ctx->query_buf_rays * sizeof(rt_occlusion_ray);
+    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
+    unsigned char* h_occ = h_rays + ctx->query_pinned_rays * sizeof(rt_occlusion_ray);
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_rays, rays + done, n * sizeof(rt_occlusion_ray));
+        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_occlusion_ray), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run_query(ctx, d_rays, d_occ, n, true))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_occ, d_occ, n, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(occluded + done, h_occ, n);
+        done += n;
+    }
     return RT_OK;
 }
 

@@ -323,6 +323,78 @@ class Renderer:
         self._call("rt_pick", int(x), int(y), N.ptr(hit))
         return hit[0]
 
+    # ------------------------------------------------------------------ occlusion queries
+    def occluded(self, rays, t_max=None):
+        """Whether anything lies on each ray before its ``t_max`` (rt_occluded): 1 iff a primitive
+        is hit at a distance strictly below t_max (in units of |direction|, like ``HIT["t"]``),
+        against the scene as it is now, without touching anything a render reads.
+
+        ``rays``: an (n, 7) float32 array (origin, direction, t_max); an (n, 6) array with
+        ``t_max`` a scalar or an (n,) array (None: +inf, "is there any hit at all"); or a
+        ``buffers.OCCLUSION_RAY`` array. Returns an (n,) uint8 array. A CUDA torch tensor of
+        shape (n, 8) float32 (rt_occlusion_ray records) goes through rt_occluded_device instead
+        -- no host round trip, stream-ordered on the context's stream -- and returns a CUDA (n,)
+        uint8 tensor."""
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            if t_max is not None:
+                raise ValueError("device rays carry t_max in their last column")
+            return self._occluded_device(rays)
+        rays = np.asarray(rays)
+        if rays.dtype == B.OCCLUSION_RAY:
+            if t_max is not None:
+                raise ValueError("OCCLUSION_RAY records carry their own t_max")
+        else:
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] not in (6, 7) or (r.shape[1] == 7 and t_max is not None):
+                raise ValueError("rays must be (n, 7) float32, (n, 6) float32 with t_max, or an OCCLUSION_RAY array")
+            rays = np.zeros(r.shape[0], B.OCCLUSION_RAY)
+            rays["origin"] = r[:, :3]
+            rays["direction"] = r[:, 3:6]
+            if r.shape[1] == 7:
+                rays["t_max"] = r[:, 6]
+            else:
+                bound = np.asarray(np.inf if t_max is None else t_max, np.float32)
+                if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != r.shape[0]):
+                    raise ValueError("t_max must be a scalar or an (n,) array")
+                rays["t_max"] = bound
+        rays = np.ascontiguousarray(rays.reshape(-1))
+        out = np.zeros(rays.shape[0], np.uint8)
+        self._call("rt_occluded", N.ptr(rays), N.ptr(out), rays.shape[0])
+        return out
+
+    def _occluded_device(self, rays):
+        import torch
+
+        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
+        if rays.device.index != self.device:
+            raise ValueError("device rays must live on the renderer's device")
+        rays = rays.contiguous()
+        out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+        if rays.shape[0] == 0:
+            return out
+        # the stream handshake of _trace_rays_device
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
+        cur = torch.cuda.current_stream(rays.device)
+        mine.wait_stream(cur)
+        self._call("rt_occluded_device", ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                   rays.shape[0])
+        cur.wait_stream(mine)
+        return out
+
+    def occluded_segments(self, a, b):
+        """Whether anything lies strictly before ``b`` on the way from ``a``, per pair of (n, 3)
+        float32 points: the ray origin = a, direction = b - a (in f32), t_max = 1."""
+        a = np.ascontiguousarray(a, np.float32)
+        b = np.ascontiguousarray(b, np.float32)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape != b.shape:
+            raise ValueError("a and b must both be (n, 3) float32")
+        rays = np.zeros(a.shape[0], B.OCCLUSION_RAY)
+        rays["origin"] = a
+        rays["direction"] = b - a
+        rays["t_max"] = 1.0
+        return self.occluded(rays)
+
     def update_texture(self, alignment: int = 256) -> np.ndarray:
         """``Renderer::update_texture`` (src/renderer.rs:254-283), headless: the
         packed output as the Rgba8Unorm display texture the reference copies it

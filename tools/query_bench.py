@@ -15,6 +15,14 @@ rays from rt_ray_count): the yardstick a query is held against (DESIGN.md §5.4b
 instance (scene read from global memory) and with the staged placement the scene takes
 (tuning "query_lds_mode" 0 against 2): where they cross is the kQueryStageMinRays threshold.
 Every mode returns the same bits; the sweep checks that on each n.
+--occluded: the occlusion kernel (rt_occluded_device) against the closest-hit call on the same
+rays in the same process. Series, each on the coherent and the permuted camera
+rays: (a) rt_trace_rays_device, the yardstick; (b) rt_occluded_device with t_max = +inf (the early
+exit); (c) with each ray's own closest-hit t (every byte 0: a full search pruned from the first
+node); (d) shadow rays from each hit point, offset 1e-4 along the normal, toward one fixed
+direction, t_max = +inf. Device events around `reps` launches on the context's stream; the series
+alternate over --rounds rounds; median, minimum and maximum Mray/s per series. With --sweep: the
+placement crossover of the occlusion kernel, as the default sweep measures the closest-hit one's.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -41,16 +49,84 @@ def camera_query_rays(scene):
     return q
 
 
-def time_queries(r, rays_t, hits_t, n, reps):
-    """Seconds per rt_trace_rays_device call over the first n rays (device tensors)."""
+def time_queries(r, rays_t, hits_t, n, reps, call="rt_trace_rays_device"):
+    """Seconds per `call` over the first n rays (device tensors)."""
     args = (ctypes.c_void_p(rays_t.data_ptr()), ctypes.c_void_p(hits_t.data_ptr()), n)
-    r._call("rt_trace_rays_device", *args)  # warm-up of this shape and placement
+    r._call(call, *args)  # warm-up of this shape and placement
     r.synchronize()
     t0 = time.perf_counter()
     for _ in range(reps):
-        r._call("rt_trace_rays_device", *args)
+        r._call(call, *args)
     r.synchronize()
     return (time.perf_counter() - t0) / reps
+
+
+SHADOW_DIRECTION = (0.35, -0.85, 0.4)  # towards the sky (y points down), off every axis
+
+
+def occlusion_bench(r, args, q, dev, emit):
+    """The --occluded series (module docstring)."""
+    import torch
+
+    n = q.shape[0]
+    perm = np.random.default_rng(2024).permutation(n)
+    hits_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    occ_t = torch.empty((n,), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+
+    def upload(a):
+        t = torch.from_numpy(np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)).to(dev)
+        torch.cuda.synchronize()  # uploaded on torch's stream, read on the context's
+        return t
+
+    def launch(call, rays_t, out_t):
+        r._call(call, ctypes.c_void_p(rays_t.data_ptr()), ctypes.c_void_p(out_t.data_ptr()), rays_t.shape[0])
+
+    base = upload(q)
+    launch("rt_trace_rays_device", base, hits_t)
+    r.synchronize()
+    h = hits_t.cpu().numpy().view(B.HIT).reshape(-1)
+    hit = h["kind"] != B.HIT_MISS
+    series = {}  # name -> (call, rays tensor, output tensor, expected count of ones)
+    for order, idx in (("coherent", np.arange(n)), ("permuted", perm)):
+        rays = q[idx]
+        any_hit, own_t = rays.view(B.OCCLUSION_RAY).copy(), rays.view(B.OCCLUSION_RAY).copy()
+        any_hit["t_max"] = np.inf
+        own_t["t_max"] = h["t"][idx]
+        from_hit = idx[hit[idx]]
+        shadow = np.zeros(from_hit.shape[0], B.OCCLUSION_RAY)
+        shadow["origin"] = h["position"][from_hit] + np.float32(1e-4) * h["normal"][from_hit]
+        shadow["direction"] = np.asarray(SHADOW_DIRECTION, np.float32)
+        shadow["t_max"] = np.inf
+        series["a_closest_hit/" + order] = ("rt_trace_rays_device", upload(rays), hits_t, None)
+        series["b_any_hit_inf/" + order] = ("rt_occluded_device", upload(any_hit), occ_t, int(hit.sum()))
+        series["c_own_t/" + order] = ("rt_occluded_device", upload(own_t), occ_t, 0)
+        if shadow.shape[0]:
+            series["d_shadow/" + order] = ("rt_occluded_device", upload(shadow), occ_t, None)
+    rates = {k: [] for k in series}
+    fraction = {}
+    for k, (call, rays_t, out_t, want) in series.items():  # warm-up and a check of what is timed
+        launch(call, rays_t, out_t)
+        r.synchronize()
+        if call == "rt_occluded_device":
+            ones = int(out_t[:rays_t.shape[0]].sum(dtype=torch.int64).item())
+            fraction[k] = ones / rays_t.shape[0]
+            assert want is None or ones == want, (k, ones, want)
+    for _ in range(args.rounds):
+        for k, (call, rays_t, out_t, _) in series.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            for _ in range(args.reps):
+                launch(call, rays_t, out_t)
+            t1.record(stream)
+            t1.synchronize()
+            rates[k].append(rays_t.shape[0] * args.reps / (t0.elapsed_time(t1) * 1e-3) / 1e6)
+    for k, v in rates.items():
+        name, order = k.split("/")
+        emit(kind="occlusion", series=name, rays_set=order, rays=int(series[k][1].shape[0]), rounds=args.rounds,
+             reps=args.reps, mray_s=round(float(np.median(v)), 1), mray_s_min=round(min(v), 1),
+             mray_s_max=round(max(v), 1), occluded_fraction=None if k not in fraction else round(fraction[k], 4),
+             hit_fraction=round(float(hit.mean()), 4), build=r._lib.rt_build_hash().decode())
 
 
 def main():
@@ -63,6 +139,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=32, help="frames of the render yardstick")
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
+    ap.add_argument("--rounds", type=int, default=7, help="--occluded: rounds the series alternate over")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "query_bench needs a HIP device"
@@ -71,6 +149,8 @@ def main():
     q = camera_query_rays(scene)
     n = q.shape[0]
     perm = np.random.default_rng(2024).permutation(n)
+    if args.occluded:  # (rt_occlusion_ray: t_max where rt_query_ray pads; +inf, "any hit at all")
+        q["_pad1"] = np.inf
     sets = {"coherent": q, "incoherent": np.ascontiguousarray(q[perm])}
     tensors = {k: torch.from_numpy(v.view(np.float32).reshape(-1, 8)).to(dev) for k, v in sets.items()}
     hits_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
@@ -82,19 +162,22 @@ def main():
         lines.append(rec)
         print(json.dumps(rec), flush=True)
 
+    call = "rt_occluded_device" if args.occluded else "rt_trace_rays_device"
     with Renderer(scene) as r:
-        if args.sweep:
+        if args.occluded and not args.sweep:
+            occlusion_bench(r, args, q, dev, emit)
+        elif args.sweep:
             sizes = [s for s in (64, 256, 1024, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 1048576) if s < n] + [n]
             for m in sizes:
                 row, ref = {}, None
                 for name, mode in (("mode0", 0), ("staged", 2)):
                     r.set_tuning("query_lds_mode", mode)
                     reps = max(args.reps, min(400, (1 << 22) // m))
-                    row[name + "_us"] = round(time_queries(r, tensors["coherent"], hits_t, m, reps) * 1e6, 2)
+                    row[name + "_us"] = round(time_queries(r, tensors["coherent"], hits_t, m, reps, call) * 1e6, 2)
                     got = hits_t[:m].cpu().numpy().tobytes()
                     ref = got if ref is None else ref
                     assert got == ref, "placements disagree"
-                emit(kind="sweep", rays=m, **row)
+                emit(kind="sweep", call=call, rays=m, **row)
             r.set_tuning("query_lds_mode", -1)
         else:
             for name, t in tensors.items():
