@@ -46,7 +46,9 @@ extern "C" {
 /* History: ... 11 (device display copy, default frame batch), 12 (tuning keys instead of
  * environment variables); 12, additive: ray queries (rt_trace_rays, rt_trace_rays_device,
  * rt_pick, rt_query_ray, rt_hit -- nothing earlier changed, so the number stays); 12,
- * additive: occlusion queries (rt_occluded, rt_occluded_device, rt_occlusion_ray). */
+ * additive: occlusion queries (rt_occluded, rt_occluded_device, rt_occlusion_ray); 12,
+ * additive: denoiser (rt_compute_features, rt_read_features, rt_features_device, rt_denoise,
+ * rt_read_denoised, rt_copy_denoised_to_device, rt_denoise_params). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -417,6 +419,126 @@ _Static_assert(sizeof(rt_occlusion_ray) == 32, "rt_occlusion_ray is 32 bytes");
 RT_API int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count);
 RT_API int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count);
 
+/* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
+ *
+ * What an interactive host shows right after the camera or the scene moved: the reference resets
+ * the accumulation on every edit and then displays a handful of samples per pixel. Two pieces:
+ * the first-hit feature buffers (normal, depth, albedo: the "AOVs" a compositor or an external
+ * denoiser also wants) and an edge-avoiding a-trous filter guided by them.
+ *
+ * FEATURES. Two float4 planes of width*height pixels, row-major:
+ *   normal_depth: normal.xyz, t        albedo_hit: albedo.rgb, hit (1.0f or 0.0f)
+ * Per pixel, the un-jittered camera ray exactly as rt_pick defines it and the record
+ * rt_trace_rays returns for it. Hit: normal and t straight from the record; albedo is
+ * sample_texture(materials[min(material_index, material_count-1)].texture_index, u, v).rgb with
+ * the clamp, sRGB table and layer clamp of the path kernel's shading (compute_shader.wgsl:26-40);
+ * emission is ignored. Miss: normal = 0, t = 3.4028235e38f, hit = 0, albedo = the environment
+ * texel at environment_map_coords(direction) (compute_shader.wgsl:580-585). Every value is
+ * bit-identical to the reference's arithmetic for that ray (exactness domain: the ray queries').
+ * The planes depend only on camera, geometry, materials, textures and Params: the context keeps a
+ * scene epoch that every rt_update_*, rt_upload_*, rt_update_camera*, rt_update_ray_directions,
+ * rt_reset_accumulation, rt_set_object_models and rt_update_objects call bumps, and recomputes the
+ * planes only when the epoch they were built at is stale. The frame is traced in bands of tuning
+ * "feature_band" pixels (96 B of scratch per pixel of a band). Like a ray query, computing the
+ * features changes nothing a render observes and leaves queued frames queued.
+ *
+ * rt_compute_features: asynchronous; a no-op when the planes are current.
+ * rt_read_features: synchronous (computes the planes if stale); either pointer may be NULL; each
+ *   receives width*height*4 floats.
+ * rt_features_device: the planes' device pointers (computed if stale, stream-ordered on
+ *   rt_stream(ctx)); valid until rt_destroy, rewritten by the next recomputation.
+ *
+ * THE FILTER. The arithmetic below is the contract.
+ *
+ * Everything is f32, one IEEE operation per written operation, in the written order.
+ *
+ * Inputs. Per pixel p:
+ *   c0(p) = accumulation(p) / D, all four channels;
+ *   D = (float)((k-1) * compute_per_frame);
+ *   k is the context's accumulation counter, as reported by rt_accumulation_index;
+ *   n(p), z(p), a(p), hit(p) from the feature planes.
+ *
+ * Host-side constants, computed in f32:
+ *   N = (k-1)*compute_per_frame;
+ *   s0 = sigma_color / sqrtf((float)N);
+ *   k_a = 1.0f / (sigma_albedo*sigma_albedo);
+ *   for iteration i: s_i = s0 * 0.5f^i (exact scaling) and k_c = 1.0f / (s_i*s_i).
+ *
+ * Iteration i = 0 .. iterations-1:
+ *   step s = 1<<i;
+ *   h = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *   taps q = p + s*(dx,dy);
+ *   dy is the outer loop and dx the inner loop, each running -2..2 ascending.
+ *
+ * Centre tap. w = h[2]*h[2] (that is 9/64). It is always taken and evaluates no guide.
+ *
+ * Other taps. A tap is skipped (it adds nothing to either sum) if q is outside the image. Otherwise:
+ *   Guide g:
+ *     If hit(p) and hit(q) are both 0, then g = 1.
+ *     If exactly one of them is 0, then g = 0.
+ *     Otherwise g = wn*wz, with:
+ *       d = max(0, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z);
+ *       wn = d^32, by five squarings;
+ *       x = |z_p - z_q| / (sigma_depth*(z_p + z_q) + 1e-30f);
+ *       wz = 1/(1 + x*x).
+ *   Albedo:
+ *     da = a_p - a_q;
+ *     xa = ((da.r*da.r + da.g*da.g) + da.b*da.b) * k_a;
+ *     ra = 1/(1+xa).
+ *   Colour, on the current iteration's input:
+ *     dc = c_p.rgb - c_q.rgb;
+ *     xc = ((dc.r*dc.r + dc.g*dc.g) + dc.b*dc.b) * k_c;
+ *     rc = 1/(1+xc).
+ *   Weight: w = (((h[dy]*h[dx]) * g) * (ra*ra)) * (rc*rc).
+ *   The tap is skipped unless w > 0. That test is false for NaN.
+ *
+ * Result per iteration. Per channel, num = num + w*c_q and den = den + w, in tap order starting
+ * from 0. The result is num/den.
+ *
+ * After the last iteration the f32 RGBA result is kept. Its clamp01 then pack_to_u32 (the
+ * truncating pack the frame output uses) goes to a separate denoised-output buffer.
+ * iterations == 0 is just c0 and its pack. That pack equals rt_read_output of the same frame.
+ * Pixels whose accumulation is not finite give unspecified values there only.
+ *
+ * The 1/sqrt(N) scaling narrows the colour weight as the accumulation converges: the filter
+ * smooths hard at 1 sample per pixel and fades out as the noise does.
+ *
+ * rt_denoise is an observation point, like rt_copy_output_to_device: queued frames launch first,
+ * then the features are computed if stale, then the filter runs, all stream-ordered on
+ * rt_stream(ctx); asynchronous. It changes nothing a render observes: the accumulation,
+ * rt_read_output, k, rt_ray_count, the timing totals and the tile schedule are untouched, and
+ * rendering continues afterwards as if it had not been called. Its buffers (two colour planes, the
+ * packed output, the feature planes and a band of scratch) are allocated on first use and freed by
+ * rt_destroy. params == NULL: rt_denoise_default_params. Tuning "denoise_lds" selects how the
+ * passes with step 1 and 2 read their taps (same bits either way).
+ * RT_E_INVALID: no frame since the last reset (k-1 == 0, or N == 0); Params.accumulate != 1 (the accumulation
+ * is never written then); iterations > 8; a sigma that is not finite or <= 0; a rank context
+ * (world_size > 1).
+ * rt_read_denoised: synchronous; the last rt_denoise's packed RGBA8 (width*height u32) and f32 RGBA
+ *   (width*height*4 floats) results; either pointer may be NULL. RT_E_INVALID before any rt_denoise.
+ * rt_copy_denoised_to_device: rt_copy_output_to_device for the packed denoised output, with the
+ *   same arguments and errors; RT_E_INVALID before any rt_denoise. Asynchronous. */
+typedef struct rt_denoise_params {
+    uint32_t iterations;   /* a-trous iterations, 0..8 (step 1, 2, 4, ...) */
+    float sigma_color;     /* colour tolerance at 1 sample per pixel */
+    float sigma_albedo;
+    float sigma_depth;     /* relative depth tolerance */
+} rt_denoise_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
+#endif
+
+RT_API int rt_denoise_default_params(rt_denoise_params* out); /* {4, 1.0f, 0.1f, 0.05f} */
+RT_API int rt_compute_features(rt_ctx* ctx);
+RT_API int rt_read_features(rt_ctx* ctx, float* normal_depth, float* albedo_hit);
+RT_API int rt_features_device(rt_ctx* ctx, const void** normal_depth, const void** albedo_hit);
+RT_API int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
+RT_API int rt_read_denoised(rt_ctx* ctx, uint32_t* rgba8_out, float* rgba_f32_out);
+RT_API int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row);
+
 /* Readback (new: the reference only blits output_data to the swapchain,
  * src/renderer.rs:254-283). Synchronous; whole framebuffer, row-major
  * width*height. Pixels of tiles owned by another rank are left as they were
@@ -508,7 +630,9 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "primary_waves" 8|0, "primary_tile_major" 1|0;
  *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays and rt_occluded),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
- *   0..2: the highest LDS staging mode of the query and occlusion kernels, falling back as a dispatch does).
+ *   0..2: the highest LDS staging mode of the query and occlusion kernels, falling back as a dispatch does);
+ *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),
+ *   "denoise_lds" 1|0 (1: the filter passes with step 1 and 2 stage tile + halo in LDS, 0: direct loads).
  * RT_E_INVALID for an unknown key or a value out of range. */
 RT_API int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value);
 

@@ -95,7 +95,13 @@ class rt_hit(ctypes.Structure):
                 ("sub_object", ctypes.c_uint32), ("triangle", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class rt_denoise_params(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma_color", ctypes.c_float),
+                ("sigma_albedo", ctypes.c_float), ("sigma_depth", ctypes.c_float)]
+
+
 assert ctypes.sizeof(rt_params) == 48
+assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
 assert ctypes.sizeof(rt_ray_camera) == 16
@@ -137,6 +143,13 @@ SIGNATURES = {
     "rt_pick": (ctypes.c_int, [_P, _U32, _U32, _P]),
     "rt_occluded": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_occluded_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_denoise_default_params": (ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
+    "rt_compute_features": (ctypes.c_int, [_P]),
+    "rt_read_features": (ctypes.c_int, [_P, _P, _P]),
+    "rt_features_device": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    "rt_denoise": (ctypes.c_int, [_P, ctypes.POINTER(rt_denoise_params)]),
+    "rt_read_denoised": (ctypes.c_int, [_P, _P, _P]),
+    "rt_copy_denoised_to_device": (ctypes.c_int, [_P, _P, _U32]),
     "rt_read_output_pitched": (ctypes.c_int, [_P, _P, _U32]),
     "rt_bytes_per_row": (_U32, [_U32, _U32]),
     "rt_ray_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),

@@ -63,6 +63,14 @@ hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
                                uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
+hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
+hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
+                                     const void* hits, float4* plane_a, float4* plane_b, hipStream_t stream);
+hipError_t rt_launch_denoise_init(const float4* accum, float4* dst, uint32_t* packed, uint64_t n, float div,
+                                  hipStream_t stream);
+hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
+                                  uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
+                                  float sigma_depth, bool lds, hipStream_t stream);
 hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
                              uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
                              uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
@@ -85,6 +93,7 @@ static_assert(sizeof(rt_object_info) == 48, "ObjectInfo is 48 bytes");
 static_assert(sizeof(rt_sub_object_info) == 32, "SubObjectInfo is 32 bytes");
 static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
+static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
 static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
@@ -157,6 +166,12 @@ constexpr uint32_t kMaxQueryChunk = 1u << 24;
 // A query of fewer rays than this launches the mode-0 instance (the scene read from global
 // memory) instead of staging the LDS image in every workgroup: measured crossover, DESIGN.md §5.4b.
 constexpr uint64_t kQueryStageMinRays = 262144;
+// Feature buffers (denoise.hip): the frame's camera rays are traced in bands of this many pixels,
+// so the scratch of a band -- its rays and records, 96 B per pixel: 48 MiB -- does not grow with
+// the frame (3840x2160 would take 800 MB at once); tuning "feature_band".
+constexpr uint32_t kDefaultFeatureBand = 1u << 19;
+constexpr uint32_t kMaxFeatureBand = 1u << 24;
+constexpr uint32_t kMaxDenoiseIterations = 8;
 
 }  // namespace
 
@@ -394,6 +409,21 @@ struct rt_ctx {
     bool q_occ_tris = false;
     size_t q_occ_lds = 0;
     int q_occ_blocks = 0;
+
+    // first-hit feature buffers and the denoiser (rt_compute_features, rt_denoise; denoise.hip).
+    // scene_epoch counts the calls that can change what a camera ray hits or what it looks up
+    // there (camera, geometry, materials, textures, Params); the planes are rebuilt when the
+    // epoch they were built at is stale. Everything is allocated on first use.
+    uint64_t scene_epoch = 1;
+    uint64_t feat_epoch = 0;                      // 0: never built
+    float4* d_feat[2] = {};                       // plane A: normal.xyz, t; plane B: albedo.rgb, hit
+    void* d_feat_scratch = nullptr;               // one band's rays, then its records
+    size_t feat_scratch_bytes = 0;
+    uint32_t feature_band = kDefaultFeatureBand;  // tuning "feature_band": pixels per band
+    float4* d_dn[2] = {};                         // the filter's ping-pong colour planes
+    uint32_t* d_dn_out = nullptr;                 // the packed denoised output
+    int dn_result = -1;                           // which of d_dn holds the last rt_denoise's result; -1: none yet
+    bool denoise_lds = true;                      // tuning "denoise_lds" 0: the passes with step 1, 2 load directly
 
     std::string err;
 };
@@ -862,7 +892,8 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf};
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -912,6 +943,7 @@ static int flush_frames(rt_ctx* ctx) {
 
 int rt_upload_textures(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height, uint32_t layers) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (!rgba8 || width == 0 || height == 0 || layers == 0)
         return fail(ctx, RT_E_INVALID, "textures: need non-empty RGBA8 data");
     const size_t texels = (size_t)width * height * layers;
@@ -929,6 +961,7 @@ int rt_upload_textures(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32
 
 int rt_upload_env_map(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (!rgba8 || width == 0 || height == 0) return fail(ctx, RT_E_INVALID, "env map: need non-empty RGBA8 data");
     const size_t texels = (size_t)width * height;
     if (texels != (size_t)ctx->env_w * ctx->env_h || !ctx->d_env) {
@@ -961,6 +994,7 @@ int rt_upload_env_map(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_
 
 int rt_update_params(rt_ctx* ctx, const rt_params* params) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     int rc = check_params(ctx, params);
     if (rc) return rc;
     ctx->params = *params;
@@ -969,6 +1003,7 @@ int rt_update_params(rt_ctx* ctx, const rt_params* params) {
 
 int rt_reset_accumulation(rt_ctx* ctx, const rt_params* params) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     int rc = check_params(ctx, params);
     if (rc) return rc;
     RT_HIP(ctx, hipMemsetAsync(ctx->d_accum, 0, ctx->n_pixels * 16, ctx->stream));
@@ -979,6 +1014,7 @@ int rt_reset_accumulation(rt_ctx* ctx, const rt_params* params) {
 
 int rt_update_ray_directions(rt_ctx* ctx, const rt_ray* rays, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !rays) return fail(ctx, RT_E_INVALID, "rays is NULL");
     if (count > ctx->n_pixels) return fail(ctx, RT_E_CAPACITY, "more rays than pixels");
     ctx->gen_rays = false;
@@ -987,6 +1023,7 @@ int rt_update_ray_directions(rt_ctx* ctx, const rt_ray* rays, uint32_t count) {
 
 int rt_update_camera_matrices(rt_ctx* ctx, const float inverse_projection[16], const float inverse_view[16]) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (!inverse_projection || !inverse_view) return fail(ctx, RT_E_INVALID, "matrix is NULL");
     std::memcpy(ctx->inv_proj, inverse_projection, sizeof(ctx->inv_proj));
     std::memcpy(ctx->inv_view, inverse_view, sizeof(ctx->inv_view));
@@ -996,6 +1033,7 @@ int rt_update_camera_matrices(rt_ctx* ctx, const float inverse_projection[16], c
 
 int rt_update_camera(rt_ctx* ctx, const rt_ray_camera* camera) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (!camera) return fail(ctx, RT_E_INVALID, "camera is NULL");
     ctx->camera = *camera;  // passed by value to the next launch
     return RT_OK;
@@ -1003,6 +1041,7 @@ int rt_update_camera(rt_ctx* ctx, const rt_ray_camera* camera) {
 
 int rt_update_spheres(rt_ctx* ctx, const rt_scene_sphere* spheres, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !spheres) return fail(ctx, RT_E_INVALID, "spheres is NULL");
     if (count > ctx->cap_sph) return fail(ctx, RT_E_CAPACITY, "more spheres than the buffer holds");
     return upload_spheres(ctx, spheres, count);
@@ -1010,6 +1049,7 @@ int rt_update_spheres(rt_ctx* ctx, const rt_scene_sphere* spheres, uint32_t coun
 
 int rt_update_triangles(rt_ctx* ctx, const rt_scene_triangle* triangles, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !triangles) return fail(ctx, RT_E_INVALID, "triangles is NULL");
     if (count > ctx->cap_tri) return fail(ctx, RT_E_CAPACITY, "more triangles than the buffer holds");
     return upload_triangles(ctx, triangles, count);
@@ -1017,6 +1057,7 @@ int rt_update_triangles(rt_ctx* ctx, const rt_scene_triangle* triangles, uint32_
 
 int rt_update_object_info(rt_ctx* ctx, const rt_object_info* objects, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !objects) return fail(ctx, RT_E_INVALID, "objects is NULL");
     if (count > ctx->cap_obj) return fail(ctx, RT_E_CAPACITY, "more objects than the buffer holds");
     int rc0 = sync_host_geometry(ctx);
@@ -1044,6 +1085,7 @@ int rt_update_object_info(rt_ctx* ctx, const rt_object_info* objects, uint32_t c
 
 int rt_update_sub_object_info(rt_ctx* ctx, const rt_sub_object_info* sub_objects, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !sub_objects) return fail(ctx, RT_E_INVALID, "sub_objects is NULL");
     if (count > ctx->cap_sub) return fail(ctx, RT_E_CAPACITY, "more sub-objects than the buffer holds");
     int rc0 = sync_host_geometry(ctx);
@@ -1065,6 +1107,7 @@ int rt_update_sub_object_info(rt_ctx* ctx, const rt_sub_object_info* sub_objects
 
 int rt_update_materials(rt_ctx* ctx, const rt_scene_material* materials, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !materials) return fail(ctx, RT_E_INVALID, "materials is NULL");
     if (count > ctx->cap_mat) return fail(ctx, RT_E_CAPACITY, "more materials than the buffer holds");
     return upload_raw(ctx, ctx->d_mat, materials, (size_t)count * 32);
@@ -1925,6 +1968,145 @@ int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit) {
     return RT_OK;
 }
 
+// ---- feature buffers and the denoiser (denoise.hip) ---------------------------------------------
+//
+// The feature planes are a whole-frame ray query: rt_feature_rays_kernel writes a band's un-jittered
+// camera rays (rt_pick's ray for every pixel), run_query traces them with the unchanged query
+// kernel, rt_feature_resolve_kernel looks up albedo or environment and writes the planes. Like a
+// query it reads the scene and writes only its own buffers.
+static int build_features(rt_ctx* ctx) {
+    if (ctx->feat_epoch == ctx->scene_epoch && ctx->d_feat[0]) return RT_OK;
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    for (float4*& plane : ctx->d_feat)
+        if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    const uint64_t band = std::min<uint64_t>(ctx->n_pixels, ctx->feature_band);
+    if ((rc = grow_buffer(ctx, &ctx->d_feat_scratch, &ctx->feat_scratch_bytes,
+                          band * (sizeof(rt_query_ray) + sizeof(rt_hit)))))
+        return rc;
+    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_feat_scratch);
+    unsigned char* d_hits = d_rays + band * sizeof(rt_query_ray);
+    KernelArgs kb{};
+    scene_base_args(ctx, kb);
+    kb.camera_rays = ctx->d_rays;
+    for (uint64_t first = 0; first < ctx->n_pixels; first += band) {  // bands reuse the scratch in stream order
+        const uint32_t n = (uint32_t)std::min<uint64_t>(band, ctx->n_pixels - first);
+        RT_HIP(ctx, rt_launch_feature_rays(kb, (uint32_t)first, n, d_rays, ctx->stream));
+        if ((rc = run_query(ctx, d_rays, d_hits, n))) return rc;
+        RT_HIP(ctx, rt_launch_feature_resolve(kb, (uint32_t)first, n, d_rays, d_hits, ctx->d_feat[0], ctx->d_feat[1],
+                                              ctx->stream));
+    }
+    ctx->feat_epoch = ctx->scene_epoch;
+    ctx->primary_dirty = true;
+    return RT_OK;
+}
+
+int rt_compute_features(rt_ctx* ctx) {
+    RT_ENTER_NOFLUSH(ctx);  // like a query: the queued frames stay queued
+    return build_features(ctx);
+}
+
+int rt_read_features(rt_ctx* ctx, float* normal_depth, float* albedo_hit) {
+    RT_ENTER_NOFLUSH(ctx);
+    const int rc = build_features(ctx);
+    if (rc) return rc;
+    float* dst[2] = {normal_depth, albedo_hit};
+    for (int i = 0; i < 2; i++)
+        if (dst[i])
+            RT_HIP(ctx, hipMemcpyAsync(dst[i], ctx->d_feat[i], ctx->n_pixels * 16, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_features_device(rt_ctx* ctx, const void** normal_depth, const void** albedo_hit) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!normal_depth || !albedo_hit) return fail(ctx, RT_E_INVALID, "rt_features_device: NULL argument");
+    const int rc = build_features(ctx);
+    if (rc) return rc;
+    *normal_depth = ctx->d_feat[0];
+    *albedo_hit = ctx->d_feat[1];
+    return RT_OK;
+}
+
+int rt_denoise_default_params(rt_denoise_params* out) {
+    if (!out) return RT_E_INVALID;
+    *out = rt_denoise_params{4u, 1.0f, 0.1f, 0.05f};
+    return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params) {
+    RT_ENTER(ctx);  // an observation point: the queued frames are launched first
+    rt_denoise_params dp;
+    (void)rt_denoise_default_params(&dp);
+    if (params) dp = *params;
+    if (ctx->world > 1)
+        return fail(ctx, RT_E_INVALID, "rt_denoise: a rank context (world_size > 1) has no full frame");
+    if (ctx->params.accumulate != 1u)
+        return fail(ctx, RT_E_INVALID, "rt_denoise: Params.accumulate != 1 never writes the accumulation");
+    if (ctx->k - 1u == 0u || (ctx->k - 1u) * ctx->params.compute_per_frame == 0u)  // D would be 0
+        return fail(ctx, RT_E_INVALID, "rt_denoise: no frame since the last reset");
+    if (dp.iterations > kMaxDenoiseIterations)
+        return fail(ctx, RT_E_INVALID, "rt_denoise: iterations must be <= " + std::to_string(kMaxDenoiseIterations));
+    for (float sgm : {dp.sigma_color, dp.sigma_albedo, dp.sigma_depth})
+        if (!std::isfinite(sgm) || !(sgm > 0.0f))
+            return fail(ctx, RT_E_INVALID, "rt_denoise: every sigma must be finite and > 0");
+    int rc = build_features(ctx);
+    if (rc) return rc;
+    for (float4*& plane : ctx->d_dn)
+        if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    if (!ctx->d_dn_out && (rc = dev_alloc(ctx, &ctx->d_dn_out, ctx->n_pixels))) return rc;
+    // the host-side constants of the contract (denoise.hip), in f32
+    const uint32_t n_samples = (ctx->k - 1u) * ctx->params.compute_per_frame;
+    const float div = (float)n_samples;
+    const float s0 = dp.sigma_color / sqrtf((float)n_samples);
+    const float k_a = 1.0f / (dp.sigma_albedo * dp.sigma_albedo);
+    RT_HIP(ctx, rt_launch_denoise_init(ctx->d_accum, ctx->d_dn[0], dp.iterations == 0 ? ctx->d_dn_out : nullptr,
+                                       ctx->n_pixels, div, ctx->stream));
+    float scale = 1.0f;
+    for (uint32_t i = 0; i < dp.iterations; i++, scale *= 0.5f) {
+        const float s_i = s0 * scale;
+        const float k_c = 1.0f / (s_i * s_i);
+        const bool last = i + 1 == dp.iterations;
+        RT_HIP(ctx, rt_launch_denoise_pass(ctx->d_feat[0], ctx->d_feat[1], ctx->d_dn[i & 1u], ctx->d_dn[(i + 1u) & 1u],
+                                           last ? ctx->d_dn_out : nullptr, ctx->width, ctx->height, 1u << i, k_a, k_c,
+                                           dp.sigma_depth, ctx->denoise_lds, ctx->stream));
+    }
+    ctx->dn_result = (int)(dp.iterations & 1u);
+    return RT_OK;
+}
+
+int rt_read_denoised(rt_ctx* ctx, uint32_t* rgba8_out, float* rgba_f32_out) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (ctx->dn_result < 0) return fail(ctx, RT_E_INVALID, "rt_read_denoised: no rt_denoise yet");
+    if (rgba8_out)
+        RT_HIP(ctx, hipMemcpyAsync(rgba8_out, ctx->d_dn_out, ctx->n_pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba_f32_out)
+        RT_HIP(ctx, hipMemcpyAsync(rgba_f32_out, ctx->d_dn[ctx->dn_result], ctx->n_pixels * 16, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!dst_device) return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: dst_device is NULL");
+    if (ctx->dn_result < 0) return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: no rt_denoise yet");
+    {
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, dst_device);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID,
+                        "rt_copy_denoised_to_device: dst_device is not device memory of the context's device");
+        }
+    }
+    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
+        return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: bytes_per_row < 4 * width");
+    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_dn_out, 4u * (size_t)ctx->width,
+                                 4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
 // ---- occlusion queries (occlusion.hip) ---------------------------------------------------------
 //
 // The any-hit counterpart of the calls above, with the same scene visibility and the same absence
@@ -2004,6 +2186,7 @@ uint32_t rt_bytes_per_row(uint32_t width, uint32_t alignment) {
 
 int rt_set_object_models(rt_ctx* ctx, const float* points, uint32_t triangle_count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (triangle_count && !points) return fail(ctx, RT_E_INVALID, "normalized_points is NULL");
     if (triangle_count > ctx->cap_tri) return fail(ctx, RT_E_CAPACITY, "more triangles than the buffer holds");
     int rc = sync_host_geometry(ctx);
@@ -2049,6 +2232,7 @@ int rt_set_object_models(rt_ctx* ctx, const float* points, uint32_t triangle_cou
 
 int rt_update_objects(rt_ctx* ctx, const rt_object_transform* transforms, uint32_t count) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (count && !transforms) return fail(ctx, RT_E_INVALID, "transforms is NULL");
     if (count > ctx->h_obj.size()) return fail(ctx, RT_E_CAPACITY, "more transforms than objects");
     if (count == 0) return RT_OK;
@@ -2142,6 +2326,7 @@ int rt_ray_count(rt_ctx* ctx, uint64_t* out) {
 
 int rt_set_brute_force(rt_ctx* ctx, int enable) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (enable < 0 || enable > 2) return fail(ctx, RT_E_INVALID, "brute-force mode must be 0, 1 or 2");
     ctx->brute = enable;
     return RT_OK;
@@ -2149,6 +2334,7 @@ int rt_set_brute_force(rt_ctx* ctx, int enable) {
 
 int rt_set_triangle_pruning(rt_ctx* ctx, int mode) {
     RT_ENTER(ctx);
+    ++ctx->scene_epoch;  // the feature planes (rt_compute_features) are stale
     if (mode < 0 || mode > 2) return fail(ctx, RT_E_INVALID, "triangle pruning mode must be 0, 1 or 2");
     ctx->tri_prune_mode = mode;
     return RT_OK;
@@ -2262,6 +2448,10 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         if ((rc = range(1, (int32_t)kMaxQueryChunk)) == RT_OK) ctx->query_chunk = (uint32_t)v;
     } else if (k == "query_lds_mode") {
         if ((rc = range(-1, 2)) == RT_OK) ctx->query_lds_mode = v;
+    } else if (k == "feature_band") {
+        if ((rc = range(64, (int32_t)kMaxFeatureBand)) == RT_OK) ctx->feature_band = (uint32_t)v;
+    } else if (k == "denoise_lds") {
+        rc = flag(ctx->denoise_lds);
     } else if (k == "batch_memory_mb") {
         if ((rc = range(1, 1 << 30)) == RT_OK) ctx->batch_budget = (size_t)v << 20;
     } else {

@@ -395,6 +395,62 @@ class Renderer:
         rays["t_max"] = 1.0
         return self.occluded(rays)
 
+    # ------------------------------------------------------------------ feature buffers & denoiser
+    def compute_features(self) -> None:
+        """rt_compute_features: the first-hit feature planes, recomputed only after a camera or
+        scene change. Asynchronous."""
+        self._call("rt_compute_features")
+
+    def features(self) -> dict:
+        """The first-hit feature buffers of the un-jittered camera rays (rt_read_features):
+        ``normal`` (H, W, 3) f32, ``depth`` (H, W) f32 (3.4028235e38 on a miss), ``albedo``
+        (H, W, 3) f32 (the environment texel on a miss), ``hit`` (H, W) f32, 1 or 0."""
+        nd = np.zeros((self.height, self.width, 4), np.float32)
+        ah = np.zeros((self.height, self.width, 4), np.float32)
+        self._call("rt_read_features", N.ptr(nd), N.ptr(ah))
+        return {"normal": np.ascontiguousarray(nd[..., :3]), "depth": np.ascontiguousarray(nd[..., 3]),
+                "albedo": np.ascontiguousarray(ah[..., :3]), "hit": np.ascontiguousarray(ah[..., 3])}
+
+    def features_device(self):
+        """(normal_depth, albedo_hit) device pointers of the two float4 planes (rt_features_device)."""
+        a, b = ctypes.c_void_p(), ctypes.c_void_p()
+        self._call("rt_features_device", ctypes.byref(a), ctypes.byref(b))
+        return a.value, b.value
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, sigma_depth=None):
+        """The guided a-trous filter over the accumulated frame (rt_denoise; the contract is in
+        include/rt_abi.h): an observation point that changes nothing a render reads. Arguments left
+        None take rt_denoise_default_params. Returns (rgba_f32 (H, W, 4), rgba8 (H, W) uint32)."""
+        p = N.rt_denoise_params()
+        N.check(None, self._lib.rt_denoise_default_params(ctypes.byref(p)), self._lib)
+        if iterations is not None:
+            p.iterations = int(iterations)
+        if sigma_color is not None:
+            p.sigma_color = float(sigma_color)
+        if sigma_albedo is not None:
+            p.sigma_albedo = float(sigma_albedo)
+        if sigma_depth is not None:
+            p.sigma_depth = float(sigma_depth)
+        self._call("rt_denoise", ctypes.byref(p))
+        return self.read_denoised()
+
+    def read_denoised(self):
+        """(rgba_f32 (H, W, 4), rgba8 (H, W) uint32) of the last ``denoise`` (rt_read_denoised)."""
+        f = np.zeros((self.height, self.width, 4), np.float32)
+        u = np.zeros((self.height, self.width), np.uint32)
+        self._call("rt_read_denoised", N.ptr(u), N.ptr(f))
+        return f, u
+
+    def denoised_image(self) -> np.ndarray:
+        """The last ``denoise`` as an (H, W, 4) RGBA8 array (R first), like ``image()``."""
+        u = np.zeros((self.height, self.width), np.uint32)
+        self._call("rt_read_denoised", N.ptr(u), None)
+        return np.ascontiguousarray(u.view(np.uint8).reshape(self.height, self.width, 4))
+
+    def copy_denoised_to_device(self, dst_device_ptr: int, bytes_per_row: int) -> None:
+        """``copy_output_to_device`` for the packed denoised output (rt_copy_denoised_to_device)."""
+        self._call("rt_copy_denoised_to_device", ctypes.c_void_p(dst_device_ptr), bytes_per_row)
+
     def update_texture(self, alignment: int = 256) -> np.ndarray:
         """``Renderer::update_texture`` (src/renderer.rs:254-283), headless: the
         packed output as the Rgba8Unorm display texture the reference copies it

@@ -1,0 +1,141 @@
+"""Time of the feature buffers and the guided a-trous denoiser (rt_compute_features, rt_denoise).
+
+usage: python tools/denoise_bench.py [--configs c2_rtiow c3_chess] [--width 1920 --height 1080]
+                                     [--reps 50] [--rounds 7] [--frames 4] [--bench-line FILE]
+                                     [--out profiles/denoise/denoise_bench.json]
+
+Per configuration, after `--frames` rendered frames and a warm-up of every series:
+
+* ms per rt_compute_features (the scene epoch is bumped before each call with an rt_update_camera
+  of the same camera, a host-only call, so every call recomputes the planes);
+* ms per rt_denoise with iterations = 0..5, the step-1 and step-2 passes LDS-tiled (tuning
+  "denoise_lds" 1) and with direct loads (0); the time of the pass with step 2^i is the difference
+  t(i+1) - t(i) of the medians (the clamp-and-pack moves from one pass to the next, so it cancels);
+* ms per whole default rt_denoise (4 iterations), both ways.
+
+Timing: device events on the context's stream around `--reps` stream-ordered calls; the series
+alternate over `--rounds` rounds (an A/B in one process, same clocks); median, minimum and maximum
+over the rounds. The spread of a series over its rounds is the run-to-run noise a difference has
+to exceed. Beside each pass: its one-touch traffic floor -- 48 B read and 16 B written per pixel
+at the HBM peak bench.py's roofline uses -- and the fraction of it achieved. `--bench-line`: a
+file holding bench.py's JSON result line, whose ms_per_step (the C2 frame) each figure is also
+given as a ratio of. The record carries the library's build hash.
+"""
+import argparse
+import ctypes
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+from rust_gpu_raytracing_amd import Renderer  # noqa: E402
+from rust_gpu_raytracing_amd import _native as N  # noqa: E402
+from rust_gpu_raytracing_amd.scene import build_config  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0  # bench.py: MI355X HBM3E peak
+PASS_BYTES_PER_PIXEL = 48 + 16
+MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16
+
+
+def main():
+    import torch
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", nargs="+", default=["c2_rtiow", "c3_chess"])
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=4)
+    ap.add_argument("--bench-line", default=None)
+    ap.add_argument("--out", default="profiles/denoise/denoise_bench.json")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "denoise_bench needs a HIP device"
+    dev = torch.device("cuda:0")
+    frame_ms = None
+    if args.bench_line:
+        for line in Path(args.bench_line).read_text().splitlines():
+            if line.startswith("{") and "ms_per_step" in line:
+                frame_ms = float(json.loads(line)["ms_per_step"])
+    record = dict(width=args.width, height=args.height, reps=args.reps, rounds=args.rounds, frames=args.frames,
+                  hbm_peak_gbs=HBM_PEAK_GBS, pass_bytes_per_pixel=PASS_BYTES_PER_PIXEL, c2_frame_ms=frame_ms,
+                  device=torch.cuda.get_device_name(0), configs={})
+    for config in args.configs:
+        scene, bounces = build_config(config, width=args.width, height=args.height)
+        with Renderer(scene) as r:
+            record["build"] = r._lib.rt_build_hash().decode()
+            stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+            for _ in range(args.frames):
+                r.compute_frame(bounces)
+            cam = N.rt_ray_camera()
+            cam.origin[:] = [float(x) for x in scene.camera.position]
+
+            def features():
+                r._call("rt_update_camera", ctypes.byref(cam))
+                r._call("rt_compute_features")
+
+            def denoise(iterations):
+                p = N.rt_denoise_params()
+                r._lib.rt_denoise_default_params(ctypes.byref(p))
+                p.iterations = iterations
+                return lambda: r._call("rt_denoise", ctypes.byref(p))
+
+            series = {"features": (None, features)}
+            for lds in (1, 0):
+                for it in range(MAX_ITERATIONS + 1):
+                    series[f"denoise_it{it}/lds{lds}"] = (lds, denoise(it))
+            results = {}
+            for name, (lds, fn) in series.items():  # warm-up of everything timed; the variants agree
+                if lds is not None:
+                    r.set_tuning("denoise_lds", lds)
+                fn()
+                r.synchronize()
+                if lds is not None:
+                    f, u = r.read_denoised()
+                    key = name.split("/")[0]
+                    if key in results:
+                        assert results[key] == (f.tobytes(), u.tobytes()), "LDS-tiled and direct passes disagree"
+                    results[key] = (f.tobytes(), u.tobytes())
+            ms = {k: [] for k in series}
+            for _ in range(args.rounds):
+                for name, (lds, fn) in series.items():
+                    if lds is not None:
+                        r.set_tuning("denoise_lds", lds)
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record(stream)
+                    for _ in range(args.reps):
+                        fn()
+                    t1.record(stream)
+                    t1.synchronize()
+                    ms[name].append(t0.elapsed_time(t1) / args.reps)
+            floor_ms = args.width * args.height * PASS_BYTES_PER_PIXEL / (HBM_PEAK_GBS * 1e9) * 1e3
+
+            def stat(v):
+                out = dict(ms=round(float(np.median(v)), 5), ms_min=round(min(v), 5), ms_max=round(max(v), 5))
+                if frame_ms:
+                    out["of_c2_frame"] = round(out["ms"] / frame_ms, 4)
+                return out
+
+            rec = dict(bounces=bounces, features=stat(ms["features"]), traffic_floor_ms_per_pass=round(floor_ms, 5))
+            for lds in (1, 0):
+                med = [float(np.median(ms[f"denoise_it{it}/lds{lds}"])) for it in range(MAX_ITERATIONS + 1)]
+                passes = {}
+                for it in range(MAX_ITERATIONS):
+                    t = med[it + 1] - med[it]
+                    passes[f"step{1 << it}"] = dict(ms=round(t, 5), floor_fraction=round(floor_ms / t, 4) if t > 0 else None,
+                                                    of_c2_frame=round(t / frame_ms, 4) if frame_ms else None)
+                rec[f"lds{lds}"] = dict(
+                    denoise_by_iterations={f"it{it}": stat(ms[f"denoise_it{it}/lds{lds}"]) for it in range(MAX_ITERATIONS + 1)},
+                    passes=passes, default_denoise=stat(ms[f"denoise_it4/lds{lds}"]))
+            record["configs"][config] = rec
+            print(json.dumps({config: rec}), flush=True)
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(record, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
