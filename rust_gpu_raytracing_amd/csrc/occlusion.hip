@@ -135,9 +135,9 @@ __device__ __forceinline__ void occlusion_begin(const SceneView& sv, const Kerne
     ts.phase = 2;
     // brute-force sphere set, as trace_begin sweeps it
     uint32_t i = 0;
-    for (; i + 4u <= ka.sphere_always; i += 4u) test_sphere_group(sv, i, o, d, ts.a4, ts.a2, ts.sph);
+    for (; i + 4u <= ka.sphere_always; i += 4u) test_sphere_group<true>(sv, i, o, d, ts.a4, ts.a2, ts.sph);
     if (ka.sphere_always - i >= 2u) {
-        test_sphere_group(sv, i, o, d, ts.a4, ts.a2, ts.sph);
+        test_sphere_group<true>(sv, i, o, d, ts.a4, ts.a2, ts.sph);
     } else if (ka.sphere_always - i == 1u) {
         float b;
         const float disc = sphere_disc(sv.sph[i], o, d, ts.a4, b);

@@ -243,6 +243,17 @@ __device__ __forceinline__ unsigned long long stamp() {
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
     return t;
 }
+// Root passes of the block group tests and the lanes in them (words 28, 29; rt_sphere_roots.h).
+struct RootPassCount {
+    unsigned long long* diag;
+    __device__ __forceinline__ void operator()() const {
+        const uint64_t pm = __ballot(true);
+        if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(pm)) {
+            atomicAdd(diag + 28, 1ull);
+            atomicAdd(diag + 29, (unsigned long long)__popcll(pm));
+        }
+    }
+};
 #endif
 
 // Dynamic LDS image, in this order (all 16-byte aligned):
@@ -711,7 +722,11 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 #endif
                     if (8u * n_wait >= kBlockLeafShare * n_tr && mode == kTrav && ts.pending != kNoLeaf) {
                         RT_ISA_MARK("sphere_leaves");
+#ifdef RT_DIAG
+                        test_sphere_group<false>(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph, RootPassCount{ka.diag});
+#else
                         test_sphere_group(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph);
+#endif
                         ts.limit = prune_limit(ts);
                         ts.pending = kNoLeaf;
                         phase_end<kTris>(sv, ka, p.o, p.d, ts);
@@ -970,7 +985,7 @@ __global__ void __launch_bounds__(kBruteThreads, kStream ? kBruteStreamWaves : k
             if (alive[k]) {
                 const float a = dot(d[k], d[k]);
                 for (uint32_t i = 0; i < ka.sphere_slot_count; i += 4u)
-                    test_sphere_group(sv, i, o[k], d[k], 4.0f * a, 2.0f * a, sph[k]);
+                    test_sphere_group<true>(sv, i, o[k], d[k], 4.0f * a, 2.0f * a, sph[k]);
             }
         }
         // check_triangles (:422-517): objects in order, their sub-objects through the LDS tiles

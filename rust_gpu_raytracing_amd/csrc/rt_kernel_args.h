@@ -101,7 +101,7 @@ constexpr uint32_t kLeafTriWords = 3 * kLeafTriSlots;       // uint4 per block (
 constexpr uint32_t kLeafBatchWaveBytes = 64 * 48;
 
 // Diagnostic counters ahead of the per-wave records in KernelArgs::diag
-// (RT_DIAG: words 0-25; RT_DIAG_TAIL: words 0-7, then 2 words per wave from here).
+// (RT_DIAG: words 0-29; RT_DIAG_TAIL: words 0-7, then 2 words per wave from here).
 constexpr uint32_t kDiagHeaderWords = 32;
 
 struct KernelArgs {

@@ -11,6 +11,7 @@
 #include "rt_bvh_slab.h"
 #include "rt_device_math.h"
 #include "rt_kernel_args.h"
+#include "rt_sphere_roots.h"
 #include "tri_qnode.h"
 
 #pragma clang fp contract(off)
@@ -61,31 +62,8 @@ __device__ __forceinline__ f4 decode_texel(uint32_t texel, const float* srgb) {
               div_const((float)(texel >> 24), 255.0f, kInv255)};
 }
 
-// check_spheres, compute_shader.wgsl:355-404.
-//
-// The reference sweeps spheres in index order keeping the first of equal
-// distances (strict `<`, :391), i.e. it returns the lexicographic minimum of
-// (t, index) over spheres with disc >= 0 and t > 0. Here spheres are visited
-// in slot order (brute-force set, then BVH leaves), so acceptance compares
-// (t, original index) lexicographically, which yields the same sphere in any
-// visiting order. `orig` starts at 0 so that t == F32_MAX is never taken.
-struct SphereHit {
-    float t;
-    uint32_t orig;
-    uint32_t slot;
-};
-
-__device__ __forceinline__ void sphere_candidate(float disc, float b, float two_a, uint32_t orig, uint32_t slot,
-                                                 SphereHit& best) {
-    if (disc >= 0.0f) {
-        const float t = (-b - sqrt_rn_any(disc)) / two_a;
-        if (t > 0.0f && (t < best.t || (t == best.t && orig < best.orig))) {
-            best.t = t;
-            best.orig = orig;
-            best.slot = slot;
-        }
-    }
-}
+// check_spheres, compute_shader.wgsl:355-404: SphereHit, sphere_candidate and the root passes of a
+// group are in rt_sphere_roots.h (shared with the CPU harness).
 
 // The reference's per-sphere arithmetic (:372-379), unchanged.
 __device__ __forceinline__ float sphere_disc(const float4 s, f3 o, f3 d, float four_a, float& b) {
@@ -97,9 +75,13 @@ __device__ __forceinline__ float sphere_disc(const float4 s, f3 o, f3 d, float f
 
 // Tests the aligned group of 4 slots starting at `slot` (sphere_bvh.h: padded
 // with NaN spheres that no ray hits). All loads are issued together and the
-// four tests are independent, so the group costs one LDS round trip.
+// four discriminants are independent, so the group costs one LDS round trip;
+// the roots are then evaluated one per candidate (sphere_group_roots), not one
+// per slot position. kBySlot: the positional arms, for the wave-uniform sweep of
+// the brute-force set (rt_sphere_roots.h).
+template <bool kBySlot = false, class PassHook = SphereRootsNoHook>
 __device__ __forceinline__ void test_sphere_group(const SceneView& sv, uint32_t slot, f3 o, f3 d, float four_a,
-                                                  float two_a, SphereHit& best) {
+                                                  float two_a, SphereHit& best, PassHook pass = PassHook{}) {
     const float4 s0 = sv.sph[slot], s1 = sv.sph[slot + 1u], s2 = sv.sph[slot + 2u], s3 = sv.sph[slot + 3u];
     const uint4 og = *reinterpret_cast<const uint4*>(sv.orig + slot);
     float b[4], disc[4];
@@ -107,13 +89,11 @@ __device__ __forceinline__ void test_sphere_group(const SceneView& sv, uint32_t 
     disc[1] = sphere_disc(s1, o, d, four_a, b[1]);
     disc[2] = sphere_disc(s2, o, d, four_a, b[2]);
     disc[3] = sphere_disc(s3, o, d, four_a, b[3]);
-    // any(disc[k] >= 0): max of the four (NaN operands ignored, as `NaN >= 0` is false)
-    if (fmax_nn(fmax_nn(disc[0], disc[1]), fmax_nn(disc[2], disc[3])) >= 0.0f) {
-        sphere_candidate(disc[0], b[0], two_a, og.x, slot, best);
-        sphere_candidate(disc[1], b[1], two_a, og.y, slot + 1u, best);
-        sphere_candidate(disc[2], b[2], two_a, og.z, slot + 2u, best);
-        sphere_candidate(disc[3], b[3], two_a, og.w, slot + 3u, best);
-    }
+    const uint32_t orig[4] = {og.x, og.y, og.z, og.w};
+    if constexpr (kBySlot)
+        sphere_group_roots_by_slot(disc, b, orig, slot, two_a, best);
+    else
+        sphere_group_roots(disc, b, orig, slot, two_a, best, pass);
 }
 
 // Sphere side: lateral box inflation and depth slack from sphere_cull_bounds

@@ -74,9 +74,9 @@ __device__ __forceinline__ void trace_begin(const SceneView& sv, const KernelArg
     // (the slots after the set up to the next group boundary are NaN padding:
     // a remainder of 2-3 spheres takes one group, a lone sphere a single test)
     uint32_t i = 0;
-    for (; i + 4u <= ka.sphere_always; i += 4u) test_sphere_group(sv, i, o, d, ts.a4, ts.a2, ts.sph);
+    for (; i + 4u <= ka.sphere_always; i += 4u) test_sphere_group<true>(sv, i, o, d, ts.a4, ts.a2, ts.sph);
     if (ka.sphere_always - i >= 2u) {
-        test_sphere_group(sv, i, o, d, ts.a4, ts.a2, ts.sph);
+        test_sphere_group<true>(sv, i, o, d, ts.a4, ts.a2, ts.sph);
     } else if (ka.sphere_always - i == 1u) {
         float b;
         const float disc = sphere_disc(sv.sph[i], o, d, ts.a4, b);
@@ -140,7 +140,10 @@ constexpr bool kDeferLeaves = kTris;
 // DESIGN §5.2).
 template <bool kTris>
 constexpr bool kBlockLeaves = !kTris;
-constexpr uint32_t kBlockLeafShare = 3;
+#ifndef RT_BLOCK_LEAF_SHARE
+#define RT_BLOCK_LEAF_SHARE 3
+#endif
+constexpr uint32_t kBlockLeafShare = RT_BLOCK_LEAF_SHARE;
 // Node steps per wave-wide check of the traversal loop (the ballots of the
 // threshold and leaf-batch tests, exec-mask updates). Lanes that finish inside
 // the group idle for its remaining steps; the visit order is unchanged.
@@ -150,8 +153,18 @@ constexpr uint32_t kBlockLeafShare = 3;
 // (round 6, profiles/r06/r06l, r06o, r06p): blocks of 4 with the tests once 3/8 of the lanes wait,
 // C2 0.2481 ms per frame; 3 / 5 / 6 steps 0.2522 / 0.2503 / 0.2503; every block tested (no
 // share) at 3 / 4 / 6 / 8 / 12 steps 0.2675 / 0.2580 / 0.2575 / 0.2614 / 0.2658.
+// Again with the group test's roots evaluated per candidate (rt_sphere_roots.h;
+// profiles/sphere_roots/ab_c2_sweep.json, one process, 9 rounds, spreads <= 0.0023):
+//   blocks of 4, share 3/8 (kept)   C2 0.2383 ms per frame
+//   blocks of 3 / 5                 0.2394 / 0.2428
+//   share 2/8 / 4/8                 0.2382 / 0.2393
+// No setting beats the defaults by more than the 1% band (-DRT_SPHERE_TRAV_UNROLL=N,
+// -DRT_BLOCK_LEAF_SHARE=N build the variants).
+#ifndef RT_SPHERE_TRAV_UNROLL
+#define RT_SPHERE_TRAV_UNROLL 4
+#endif
 template <int kMode, bool kTris>
-constexpr int kTravUnroll = !kTris ? 4 : kMode <= 1 ? 5 : 3;
+constexpr int kTravUnroll = !kTris ? RT_SPHERE_TRAV_UNROLL : kMode <= 1 ? 5 : 3;
 // Triangle walks: the leaf batch runs after the block's node steps in the same iteration (round 6)
 // instead of in an iteration of its own in which the walking lanes idle: the LDS-resident walk
 // (mode 2, C3 0.2645 -> 0.2463, C4 1.539 -> 1.416 ms per frame in one process with blocks of 3

@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--frame-batch", type=int, default=8, help="rt_set_frame_batch (frames is rounded to a multiple)")
     ap.add_argument("--world", type=int, default=1, help="time rank --rank's share of an N-way tile split")
     ap.add_argument("--rank", type=int, default=0)
+    ap.add_argument("--settle-ms", type=float, default=150.0, help="as bench.py --settle-ms (DESIGN.md §6)")
     args = ap.parse_args()
     scene, bounces = build_config(args.config, width=args.width, height=args.height)
     rays_dirs = scene.camera.recalculate_ray_directions()
@@ -61,6 +62,12 @@ def main():
         for _ in range(args.frame_batch):
             r.compute_frame(bounces)
         r.synchronize()
+    t_settle = time.perf_counter()  # as bench.py: untimed frames until the clocks settle
+    while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
+        for r in rs:
+            for _ in range(args.frame_batch):
+                r.compute_frame(bounces)
+            r.synchronize()
     times = {p: [] for p in args.libs}
     walls = {p: [] for p in args.libs}
     rays = {}
@@ -85,6 +92,8 @@ def main():
     for (p, t), s in zip(times.items(), same):
         med = statistics.median(t)
         out.append({"lib": Path(p).name, "median_ms": round(med, 4), "min_ms": round(min(t), 4),
+                    # round-to-round spread of this build's own rounds (the noise a difference is read against)
+                    "spread_ms": round(max(t) - min(t), 4), "rounds_ms": [round(v, 4) for v in t],
                     "wall_ms": round(statistics.median(walls[p]), 4),
                     "mray_s": round(rays[p] / med / 1e3, 1), "bit_identical_to_first": s,
                     "launch": launch_of(rs[list(times).index(p)])})

@@ -34,7 +34,7 @@ for name in argv or list(SIZES):
         r.reset_ray_count()
         for _ in range(3 * fb):
             r.compute_frame(bounces)
-        c = r.debug_counters(28)
+        c = r.debug_counters(30)
         rays = r.ray_count()
     total, trav, steps, it, step_lanes, shade, refill, setup, leaf_cyc, leaf_steps = c[:10]
     sh_pass, sh_lanes, miss, glass, spec, su_pass, su_lanes = c[12:19]
@@ -45,6 +45,8 @@ for name in argv or list(SIZES):
     # sphere-only kernels since round 6: the group tests run once per block of unrolled node steps
     # for every lane that reached a leaf in it (words 24/25 then count node steps with a lane at a leaf)
     n_blocks, n_block_lanes = c[26:28]
+    # the root passes of those block group tests (one candidate per lane and pass) and their lanes
+    n_root_passes, n_root_lanes = c[28:30]
     trav_occ = step_lanes / max(steps, 1) / 64
     shade_occ = sh_lanes / max(sh_pass, 1) / 64
     setup_occ = su_lanes / max(su_pass, 1) / 64
@@ -62,7 +64,9 @@ for name in argv or list(SIZES):
                                             "steps_with_a_group_test": n_groups / max(n_steps, 1),
                                             "lanes_per_group_test": n_group_lanes / max(n_groups, 1),
                                             "block_group_tests_per_ray": n_blocks / rays,
-                                            "lanes_per_block_group_test": n_block_lanes / max(n_blocks, 1)},
+                                            "lanes_per_block_group_test": n_block_lanes / max(n_blocks, 1),
+                                            "root_passes_per_block_group_test": n_root_passes / max(n_blocks, 1),
+                                            "lanes_per_root_pass": n_root_lanes / max(n_root_passes, 1)},
                       "leaf_certificates_per_ray": {"checked": cert_checks / rays, "leaves_skipped": cert_leaves / rays,
                                                     "triangles_skipped": cert_tris / rays},
                       "occupancy": {"traversal": trav_occ, "shading": shade_occ, "setup": setup_occ},
