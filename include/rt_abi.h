@@ -48,7 +48,8 @@ extern "C" {
  * rt_pick, rt_query_ray, rt_hit -- nothing earlier changed, so the number stays); 12,
  * additive: occlusion queries (rt_occluded, rt_occluded_device, rt_occlusion_ray); 12,
  * additive: denoiser (rt_compute_features, rt_read_features, rt_features_device, rt_denoise,
- * rt_read_denoised, rt_copy_denoised_to_device, rt_denoise_params). */
+ * rt_read_denoised, rt_copy_denoised_to_device, rt_denoise_params);
+ * 12, additive: radiance queries (rt_radiance, rt_radiance_device, rt_radiance_ray). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -419,6 +420,90 @@ _Static_assert(sizeof(rt_occlusion_ray) == 32, "rt_occlusion_ray is 32 bytes");
 RT_API int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count);
 RT_API int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count);
 
+/* ---- radiance queries (ABI 12, additive: radiance queries) -----------------
+ *
+ * "How much light arrives along this ray?" for arbitrary rays: the path tracer's shading, RNG
+ * and bounce loop (per_pixel, compute_shader.wgsl:210-314) started from a record instead of
+ * the pinhole and a pixel. Irradiance and reflection probes, lightmap texels, thin-lens,
+ * orthographic or panoramic cameras (a different origin per ray), the light at a picked point. */
+
+/* One ray with its RNG stream. The layout of rt_query_ray with the RNG stream in the place of
+ * _pad0: one buffer can be handed to rt_trace_rays, rt_occluded and rt_radiance. 32 bytes. */
+typedef struct rt_radiance_ray {
+    float origin[3];
+    uint32_t stream;     /* takes the place of the pixel index in per_pixel's seed */
+    float direction[3];  /* need not be unit length */
+    float _pad1;         /* ignored */
+} rt_radiance_ray;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_radiance_ray) == 32, "rt_radiance_ray is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_radiance_ray) == 32, "rt_radiance_ray is 32 bytes");
+#endif
+
+/* Writes four floats per ray, in order; nothing outside [0, 4 * count) is written.
+ *
+ * For ray i with record (o, stream, d):
+ *
+ *   R = (0.0f, 0.0f, 0.0f, 0.0f)
+ *   for s = 0 .. samples-1, ascending:
+ *       L = per_pixel(compute_shader.wgsl:210-314) with
+ *             the camera origin replaced by o,
+ *             camera_rays[index] replaced by d,
+ *             seed = stream * (first_sample + s) * 326624u   (u32, wrapping; :217 with index := stream)
+ *             the loop limit `bounces`
+ *       R = R + L                                            (per channel, one f32 add, all four channels)
+ *   radiance[i] = R
+ *
+ * Everything else of per_pixel is exactly as in a frame: the three-draw jitter
+ * d += (2r-1)*0.0005 is not renormalised; the material clamp, the sRGB table, the texture
+ * clamps and the environment lookup are unchanged; so are the glass, specular and diffuse
+ * decisions and their draw order. Every value is bit-identical to the reference's arithmetic.
+ * Consequences:
+ *  - The result is the accumulation one rt_compute_frame would produce for a pixel whose index
+ *    is `stream`, whose cached direction is d and whose camera origin is o, starting from a
+ *    zeroed accumulation with accumulate = 1, compute_per_frame = samples and
+ *    accumulation_index = first_sample.
+ *  - The caller divides by `samples`. Nothing is clamped or packed.
+ *  - bounces == 0 gives all-zero radiance (the loop does not run) and is RT_OK.
+ *    samples == 0 is RT_E_INVALID (whatever `count` is).
+ *  - *segments receives the batch's counted ray segments under the rule of rt_ray_count: every
+ *    trace_ray call is counted, and a path that escapes stops counting. In the device variant
+ *    the kernel adds the batch's total into the caller's u64 (it is added to, not set: one
+ *    reduction and one atomic add per wave at exit, not one per ray).
+ *  - Exactness holds for the domain of the ray queries above, for every segment of a path:
+ *    finite components, |direction| in [1e-5, 1e5], |origin| <= 1e15. Outside it the result is
+ *    unspecified. Termination: each walk ends as a ray query's does (the
+ *    walks' skip links only advance), and a lane runs at most samples * bounces walks.
+ *
+ * Scene visibility and side effects are those of rt_trace_rays: the query sees the scene as
+ * of the call -- materials, textures and the environment map now matter too -- with the
+ * accelerators prepared exactly as a dispatch prepares them, and changes nothing a render can
+ * observe (queued frames stay queued; the accumulation, the output, the accumulation index,
+ * rt_ray_count, the timing totals, the tile schedule, the feature planes and the denoiser's
+ * buffers are untouched). The result does not depend on the brute-force mode, on any
+ * rt_set_tuning key or on triangle pruning modes 0 and 1 (mode 2 is inexact here as for
+ * frames and ray queries). It works on rank contexts (world_size > 1) as the other queries do.
+ *
+ * rt_radiance: host pointers, synchronous. Staged through the pinned buffer of rt_trace_rays
+ * in chunks of tuning "query_chunk" rays (32 bytes in, 16 bytes out per ray). `segments` may
+ * be NULL.
+ * rt_radiance_device: device pointers on the context's device; rays and radiance 16-byte
+ * aligned, segments_device (may be NULL) 8-byte aligned; stream-ordered on rt_stream(ctx), no
+ * host copy, asynchronous. RT_E_INVALID when any of them is not device memory of the context's
+ * device, as for rt_trace_rays_device.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries; by default
+ * batches of fewer than 262144 walks (count * samples) read the scene from global memory.
+ * count == 0 returns RT_OK and launches nothing; a NULL rays or radiance pointer with
+ * count > 0 is RT_E_INVALID. */
+RT_API int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance /* 4 floats per ray */,
+                       uint64_t count, uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                       uint64_t* segments /* may be NULL */);
+RT_API int rt_radiance_device(rt_ctx* ctx, const void* rays_device, void* radiance_device, uint64_t count,
+                              uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                              void* segments_device /* may be NULL; one u64, added to */);
+
 /* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
  *
  * What an interactive host shows right after the camera or the scene moved: the reference resets
@@ -628,9 +713,9 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "tri_octants" 1|0, "tri_qnodes" 1|0, "coop_leaves" 1|0, "stage_subs" 1|0,
  *   "primary_pass" -1|0|1 (-1: by scene), "primary_threads" 256|64|128|512|1024,
  *   "primary_waves" 8|0, "primary_tile_major" 1|0;
- *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays and rt_occluded),
+ *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays, rt_occluded and rt_radiance),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
- *   0..2: the highest LDS staging mode of the query and occlusion kernels, falling back as a dispatch does);
+ *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does);
  *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),
  *   "denoise_lds" 1|0 (1: the filter passes with step 1 and 2 stage tile + halo in LDS, 0: direct loads).
  * RT_E_INVALID for an unknown key or a value out of range. */

@@ -88,6 +88,11 @@ class rt_occlusion_ray(ctypes.Structure):
                 ("direction", ctypes.c_float * 3), ("t_max", ctypes.c_float)]
 
 
+class rt_radiance_ray(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_float * 3), ("stream", ctypes.c_uint32),
+                ("direction", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
+
+
 class rt_hit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
                 ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
@@ -104,6 +109,7 @@ assert ctypes.sizeof(rt_params) == 48
 assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
+assert ctypes.sizeof(rt_radiance_ray) == 32
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -143,7 +149,9 @@ SIGNATURES = {
     "rt_pick": (ctypes.c_int, [_P, _U32, _U32, _P]),
     "rt_occluded": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_occluded_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
-    "rt_denoise_default_params": (ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
+    "rt_radiance": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_radiance_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
+    "rt_denoise_default_params":(ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
     "rt_compute_features": (ctypes.c_int, [_P]),
     "rt_read_features": (ctypes.c_int, [_P, _P, _P]),
     "rt_features_device": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P)]),

@@ -114,6 +114,9 @@ HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 # rt_occlusion_ray -- occlusion queries (rt_occluded): a QUERY_RAY with the distance bound in the
 # place of _pad1; the result is one uint8 per ray
 OCCLUSION_RAY = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
+# rt_radiance_ray -- radiance queries (rt_radiance): a QUERY_RAY with the RNG stream in the place of
+# _pad0; the result is four float32 per ray
+RADIANCE_RAY = np.dtype([("origin", "<f4", 3), ("stream", "<u4"), ("direction", "<f4", 3), ("_pad1", "<f4")])
 # rt_denoise_params -- the guided a-trous filter (rt_denoise); defaults {4, 1.0, 0.1, 0.05}
 DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigma_albedo", "<f4"),
                            ("sigma_depth", "<f4")])
@@ -121,7 +124,7 @@ DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigm
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
-    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (DENOISE_PARAMS, 16),
+    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (DENOISE_PARAMS, 16),
 ):
     assert _dt.itemsize == _size, (_dt, _size)
 

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,12 @@ hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* bl
 hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
                                uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream);
+uint32_t rt_radiance_threads(int mode, bool tris);
+hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+                              const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
+                              unsigned long long* segments, uint32_t wave_chunk, uint32_t first_chunk,
+                              uint32_t first_sample, uint32_t samples, hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
@@ -95,6 +102,9 @@ static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
 static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
 static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
+static_assert(sizeof(rt_radiance_ray) == sizeof(rt_query_ray), "rt_radiance_ray is an rt_query_ray with the stream for _pad0");
+static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ray, direction) == 16,
+              "rt_radiance_ray: {origin, stream}, {direction, pad} as two 16-B loads");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
 static_assert(sizeof(rt_sub_object_info) == sizeof(RtSubObject), "sub-object record");
@@ -404,8 +414,9 @@ struct rt_ctx {
     size_t query_buf_rays = 0, query_buf_bytes = 0;
     void* query_pinned = nullptr;               // the same on the host, pinned
     size_t query_pinned_rays = 0;
+    unsigned long long* d_radiance_segs = nullptr;  // rt_radiance: the batch's counted segments
     int q_occ_mode = -1;                        // occupancy of the last query instance
-    bool q_occ_any_hit = false;                 // (of rt_occlusion_kernel, else rt_query_kernel)
+    int q_occ_kind = 0;                         // (which kernel's: QueryKind)
     bool q_occ_tris = false;
     size_t q_occ_lds = 0;
     int q_occ_blocks = 0;
@@ -892,7 +903,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -1801,8 +1812,16 @@ static int query_enter(rt_ctx* ctx) {
 
 // The scene view of a query of `count` rays: the frame launches' carve, with the placement capped
 // by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
-// `any_hit`: for rt_occlusion_kernel (occlusion.hip), else rt_query_kernel.
-static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, bool any_hit, SceneLaunch& sl, size_t* lds_bytes,
+// `kind`: the kernel the view is for -- rt_query_kernel, rt_occlusion_kernel (occlusion.hip) or
+// rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples.
+enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2 };
+
+static uint32_t query_threads(int kind, int mode, bool tris) {
+    return kind == kQueryRadiance ? rt_radiance_threads(mode, tris)
+                                  : kind == kQueryAnyHit ? rt_occlusion_threads(mode) : rt_query_threads(mode);
+}
+
+static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, SceneLaunch& sl, size_t* lds_bytes,
                        int* blocks_per_cu) {
     scene_base_args(ctx, ka);
     ka.camera_rays = ctx->d_rays;
@@ -1818,17 +1837,18 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, bool any_hit
         scene_carve(ctx, ka, max_mode, sl);
         const int rc = scene_accel_args(ctx, ka, sl);
         if (rc) return rc;
-        const uint32_t threads = any_hit ? rt_occlusion_threads(sl.mode) : rt_query_threads(sl.mode);
+        const uint32_t threads = query_threads(kind, sl.mode, sl.tris);
         ka.lds_leafbatch_offset = (uint32_t)al16(sl.lds_bytes);
         *lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
-        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_any_hit != any_hit ||
+        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_kind != kind ||
             ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != *lds_bytes) {
             int n = 0;
-            const hipError_t e = any_hit ? rt_occlusion_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
-                                         : rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
+            const hipError_t e = kind == kQueryRadiance ? rt_radiance_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
+                                 : kind == kQueryAnyHit ? rt_occlusion_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
+                                                        : rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
             if (e != hipSuccess) (void)hipGetLastError();
             ctx->q_occ_mode = sl.mode;
-            ctx->q_occ_any_hit = any_hit;
+            ctx->q_occ_kind = kind;
             ctx->q_occ_tris = sl.tris;
             ctx->q_occ_lds = *lds_bytes;
             ctx->q_occ_blocks = e == hipSuccess ? n : 0;
@@ -1850,7 +1870,7 @@ static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count, 
     SceneLaunch sl;
     size_t lds_bytes = 0;
     int per_cu = 0;
-    const int rc = query_scene(ctx, ka, count, any_hit, sl, &lds_bytes, &per_cu);
+    const int rc = query_scene(ctx, ka, count, any_hit ? kQueryAnyHit : kQueryClosest, sl, &lds_bytes, &per_cu);
     if (rc) return rc;
     const uint32_t waves_per_block = (any_hit ? rt_occlusion_threads(sl.mode) : rt_query_threads(sl.mode)) / 64u;
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
@@ -2154,6 +2174,132 @@ int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, ui
         std::memcpy(occluded + done, h_occ, n);
         done += n;
     }
+    return RT_OK;
+}
+
+// ---- radiance queries (radiance.hip) -----------------------------------------------------------
+//
+// per_pixel for arbitrary rays, with the scene visibility and the absence of side effects of the
+// calls above. rt_radiance stages through the same buffers (32 B in, 16 B out per ray: the sums go
+// where the records of a closest-hit chunk would).
+
+// Rays per chunk of a radiance launch (whole waves of rays): the cap of a wave's own first chunk
+// and of the chunks the counter deals (DESIGN.md §5.4e has the measurement behind the values).
+#ifndef RT_RADIANCE_FIRST_CHUNK_MAX
+#define RT_RADIANCE_FIRST_CHUNK_MAX 128u
+#endif
+#ifndef RT_RADIANCE_CHUNK_MAX
+#define RT_RADIANCE_CHUNK_MAX 128u
+#endif
+constexpr uint64_t kRadianceFirstChunkMax = RT_RADIANCE_FIRST_CHUNK_MAX;
+constexpr uint64_t kRadianceChunkMax = RT_RADIANCE_CHUNK_MAX;
+
+// Path-traces `count` rays at device pointer `rays` into `radiance`, stream-ordered on the primary
+// stream; the batch's counted segments are added to the device counter `segments` (null: not
+// counted).
+static int run_radiance(rt_ctx* ctx, const void* rays, void* radiance, uint64_t count, uint32_t bounces,
+                        uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
+    if (count == 0) return RT_OK;
+    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
+        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
+        return RT_OK;
+    }
+    KernelArgs ka{};
+    SceneLaunch sl;
+    size_t lds_bytes = 0;
+    int per_cu = 0;
+    // the placement threshold of the other queries, on the walks the batch runs at least
+    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
+    const int rc = query_scene(ctx, ka, walks, kQueryRadiance, sl, &lds_bytes, &per_cu);
+    if (rc) return rc;
+    ka.bounces = bounces;
+    ka.drain_threshold = ctx->drain_threshold;
+    ka.drain_min_steps = ctx->drain_min_steps;
+    const uint32_t waves_per_block = rt_radiance_threads(sl.mode, sl.tris) / 64u;
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
+    const uint64_t wanted = (count + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
+    // run_query's schedule for the occlusion kernel -- each wave's own first chunk (whole waves of
+    // rays, no claim), the counter deals the rest -- in chunks of at most 128 rays: a ray here is
+    // a whole path, so a chunk of consecutive rays is uniformly dear or cheap and larger chunks
+    // end the launch on the waves that drew the dear ones
+    const uint64_t waves = (uint64_t)blocks * waves_per_block;
+    const uint32_t first_chunk = (uint32_t)std::min<uint64_t>(
+        kRadianceFirstChunkMax, std::max<uint64_t>(64u, (count / waves / 2u) & ~63ull));
+    const uint64_t rest = count > waves * first_chunk ? count - waves * first_chunk : 0;
+    const uint32_t rest_chunk = (uint32_t)std::min<uint64_t>(
+        kRadianceChunkMax, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    const hipError_t e = rt_launch_radiance(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, radiance, count,
+                                            ctx->d_query_next, segments, rest_chunk, first_chunk, first_sample,
+                                            samples, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel launch", e);
+    return RT_OK;
+}
+
+int rt_radiance_device(rt_ctx* ctx, const void* rays_device, void* radiance_device, uint64_t count, uint32_t bounces,
+                       uint32_t first_sample, uint32_t samples, void* segments_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_radiance_device: samples is 0");
+    if (count == 0) return RT_OK;
+    if (!rays_device || !radiance_device)
+        return fail(ctx, RT_E_INVALID, "rt_radiance_device: rays or radiance is NULL");
+    for (const void* ptr : {rays_device, (const void*)radiance_device, (const void*)segments_device}) {
+        if (!ptr) continue;  // (segments may be NULL)
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID,
+                        "rt_radiance_device: rays, radiance and segments must be device memory of the context's device");
+        }
+    }
+    if (((uintptr_t)rays_device | (uintptr_t)radiance_device) & 15u)
+        return fail(ctx, RT_E_INVALID, "rt_radiance_device: rays and radiance must be 16-byte aligned");
+    if ((uintptr_t)segments_device & 7u)
+        return fail(ctx, RT_E_INVALID, "rt_radiance_device: segments must be 8-byte aligned");
+    const int rc = query_enter(ctx);
+    if (rc) return rc;
+    return run_radiance(ctx, rays_device, radiance_device, count, bounces, first_sample, samples,
+                        static_cast<unsigned long long*>(segments_device));
+}
+
+int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint64_t count, uint32_t bounces,
+                uint32_t first_sample, uint32_t samples, uint64_t* segments) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_radiance: samples is 0");
+    if (count == 0) {
+        if (segments) *segments = 0;
+        return RT_OK;
+    }
+    if (!rays || !radiance) return fail(ctx, RT_E_INVALID, "rt_radiance: rays or radiance is NULL");
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    if (!ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_rad = d_rays + ctx->query_buf_rays * sizeof(rt_radiance_ray);
+    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
+    unsigned char* h_rad = h_rays + ctx->query_pinned_rays * sizeof(rt_radiance_ray);
+    // the counter's readback lands in the pinned buffer after the chunk's sums (16 of the 64
+    // bytes per ray a closest-hit record would take)
+    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_rad + chunk * 16u);
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_rays, rays + done, n * sizeof(rt_radiance_ray));
+        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_radiance_ray), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run_radiance(ctx, d_rays, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_rad, d_rad, n * 16u, hipMemcpyDeviceToHost, ctx->stream));
+        done += n;
+        if (done == count)
+            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(radiance + 4u * (done - n), h_rad, n * 16u);
+    }
+    if (segments) *segments = *h_segs;
     return RT_OK;
 }
 

@@ -474,6 +474,21 @@ __device__ __forceinline__ void start_sample(const KernelArgs& ka, uint32_t inde
     p.bounce = 0;
 }
 
+// The same prologue for a radiance query (radiance.hip): the origin and the RNG stream come from
+// the ray's record, where start_sample takes the camera origin and the pixel index (:217 with
+// index := stream). Everything else, the unnormalised jitter included, is start_sample's.
+__device__ __forceinline__ void start_sample_at(f3 origin, uint32_t stream, uint32_t random_index, f3 dir, Path& p) {
+    p.o = origin;
+    p.d = dir;
+    p.seed = stream * random_index * 326624u;
+    const float rx = random01(p.seed), ry = random01(p.seed), rz = random01(p.seed);
+    const f3 jit = mk(rx * 2.0f - 1.0f, ry * 2.0f - 1.0f, rz * 2.0f - 1.0f);
+    p.d = p.d + jit * 0.0005f;  // not renormalised (:219)
+    p.contrib = f4{1.0f, 1.0f, 1.0f, 1.0f};
+    p.light = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    p.bounce = 0;
+}
+
 // The shading half of one iteration of the bounce loop, :228-311, given the
 // trace result. Returns true when the path is finished (escaped to the
 // environment, or the bounce limit is reached).

@@ -395,6 +395,69 @@ class Renderer:
         rays["t_max"] = 1.0
         return self.occluded(rays)
 
+    # ------------------------------------------------------------------ radiance queries
+    def radiance(self, rays, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,
+                 samples: int = 1, return_segments: bool = False):
+        """The light arriving along each ray (rt_radiance): the sum over ``samples`` samples of the
+        reference's per_pixel with the camera origin, the pixel's direction and the pixel index of
+        the seed taken from the ray's record -- what one compute_frame would add to a zeroed
+        accumulation for such a pixel with accumulation_index = ``first_sample``. Divide by
+        ``samples`` for the mean; nothing is clamped. Against the scene as it is now, without
+        touching anything a render reads.
+
+        ``rays``: an (n, 6) float32 array (origin, direction), with ``streams`` an (n,) uint32
+        array of RNG streams (default: the ray's position in the batch, as a pixel index would
+        be), or a ``buffers.RADIANCE_RAY`` array. Returns an (n, 4) float32 array, and with
+        ``return_segments`` the batch's counted ray segments (the rule of ``ray_count``). A CUDA
+        torch tensor of shape (n, 8) float32 (rt_radiance_ray records: the stream's bits in
+        column 3) goes through rt_radiance_device instead -- no host round trip, stream-ordered
+        on the context's stream -- and returns a CUDA (n, 4) float32 tensor."""
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            if streams is not None:
+                raise ValueError("device rays carry their stream in column 3")
+            return self._radiance_device(rays, bounces, first_sample, samples, return_segments)
+        rays = np.asarray(rays)
+        if rays.dtype == B.RADIANCE_RAY:
+            if streams is not None:
+                raise ValueError("RADIANCE_RAY records carry their own stream")
+        else:
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] != 6:
+                raise ValueError("rays must be (n, 6) float32 or a RADIANCE_RAY array")
+            rays = np.zeros(r.shape[0], B.RADIANCE_RAY)
+            rays["origin"] = r[:, :3]
+            rays["direction"] = r[:, 3:]
+            s = np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
+            if s.shape != (r.shape[0],):
+                raise ValueError("streams must be an (n,) array")
+            rays["stream"] = s
+        rays = np.ascontiguousarray(rays.reshape(-1))
+        out = np.zeros((rays.shape[0], 4), np.float32)
+        segments = ctypes.c_uint64(0)
+        self._call("rt_radiance", N.ptr(rays), N.ptr(out), rays.shape[0], int(bounces), int(first_sample),
+                   int(samples), ctypes.byref(segments))
+        return (out, segments.value) if return_segments else out
+
+    def _radiance_device(self, rays, bounces, first_sample, samples, return_segments):
+        import torch
+
+        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
+        if rays.device.index != self.device:
+            raise ValueError("device rays must live on the renderer's device")
+        rays = rays.contiguous()
+        out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+        segments = torch.zeros(1, dtype=torch.int64, device=rays.device) if return_segments else None
+        # the stream handshake of _trace_rays_device
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
+        cur = torch.cuda.current_stream(rays.device)
+        mine.wait_stream(cur)
+        self._call("rt_radiance_device", ctypes.c_void_p(rays.data_ptr() if rays.shape[0] else None),
+                   ctypes.c_void_p(out.data_ptr() if rays.shape[0] else None), rays.shape[0], int(bounces),
+                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
+        cur.wait_stream(mine)
+        return (out, int(segments.item())) if return_segments else out
+
     # ------------------------------------------------------------------ feature buffers & denoiser
     def compute_features(self) -> None:
         """rt_compute_features: the first-hit feature planes, recomputed only after a camera or

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Per-kernel register use / spills / occupancy of pathtrace.hip (device-only compile, a few seconds).
-# usage: tools/kernel_regs.sh [query.hip | occlusion.hip] [extra hipcc flags]
-# With a source name: every kernel of that file of csrc/ instead (rt_query_kernel / rt_occlusion_kernel
-# instances as <mode, triangles, threads>).
+# usage: tools/kernel_regs.sh [query.hip | occlusion.hip | radiance.hip] [extra hipcc flags]
+# With a source name: every kernel of that file of csrc/ instead (rt_query_kernel / rt_occlusion_kernel /
+# rt_radiance_kernel instances as <mode, triangles, threads>).
 cd "$(dirname "$0")/.." || exit 1
 src=pathtrace.hip
 case "$1" in *.hip) src=$1; shift ;; esac

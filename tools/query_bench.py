@@ -23,6 +23,16 @@ node); (d) shadow rays from each hit point, offset 1e-4 along the normal, toward
 direction, t_max = +inf. Device events around `reps` launches on the context's stream; the series
 alternate over --rounds rounds; median, minimum and maximum Mray/s per series. With --sweep: the
 placement crossover of the occlusion kernel, as the default sweep measures the closest-hit one's.
+--radiance: the radiance kernel (rt_radiance_device) against the frame it reproduces, in one process
+(DESIGN.md §5.4e). The frame's own rays -- camera origin, each pixel's direction, stream = pixel
+index, samples = 1 -- are submitted as one batch; the yardstick is the same context rendering one
+frame per launch (frame batch 1), timed on the device clock with rt_set_timing. A round renders
+`reps` frames, then queries the same samples (first_sample = each frame's accumulation index), so
+both sides trace the same segments (checked: the batch's segments equal rt_ray_count, and the
+first query equals the first frame's accumulation bit for bit); Mray/s from the segments over
+device events, and from rt_ray_count over the launch spans. The closest-hit query of the same rays
+is timed next to them. Median, minimum and maximum over --rounds rounds after --settle-ms of
+untimed work.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -129,6 +139,93 @@ def occlusion_bench(r, args, q, dev, emit):
              hit_fraction=round(float(hit.mean()), 4), build=r._lib.rt_build_hash().decode())
 
 
+def radiance_bench(r, args, scene, bounces, dev, emit):
+    """The --radiance series (module docstring)."""
+    import statistics
+
+    import torch
+
+    d = scene.camera.recalculate_ray_directions()["direction"]
+    n = d.shape[0]
+    q = np.zeros(n, B.RADIANCE_RAY)
+    q["origin"] = np.asarray(scene.camera.position, np.float32)
+    q["direction"] = d
+    q["stream"] = np.arange(n, dtype=np.uint32)
+    rays_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    out_t = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    hits_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    seg_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()  # uploaded on torch's stream, read on the context's
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+
+    def radiance(first_sample):
+        r._call("rt_radiance_device", ctypes.c_void_p(rays_t.data_ptr()), ctypes.c_void_p(out_t.data_ptr()), n, bounces,
+                first_sample, 1, ctypes.c_void_p(seg_t.data_ptr()))
+
+    def closest_hit():
+        r._call("rt_trace_rays_device", ctypes.c_void_p(rays_t.data_ptr()), ctypes.c_void_p(hits_t.data_ptr()), n)
+
+    r.set_frame_batch(1)  # the yardstick: one frame per launch
+    # what is timed is the same computation: the first frame's accumulation, bit for bit
+    r.reset_accumulation()
+    r.compute_frame(bounces)
+    acc = r.read_accumulation().reshape(n, 4)
+    frame_rays = r.ray_count()
+    radiance(1)
+    r.synchronize()
+    same = bool(np.array_equal(out_t.cpu().numpy().view(np.uint32), acc.view(np.uint32)))
+    assert same and int(seg_t.item()) == frame_rays, (same, int(seg_t.item()), frame_rays)
+    closest_hit()
+    t_settle = time.perf_counter()  # untimed work until the clocks settle
+    while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
+        r.compute_frame(bounces)
+        radiance(1)
+        r.synchronize()
+    frame_ms, rad_ms, hit_ms, frame_rate, rad_rate = [], [], [], [], []
+    for _ in range(args.rounds):
+        # frames k0 .. k0+reps-1, then the radiance queries of the same samples: the same segments
+        k0 = r.accumulation_index
+        r.reset_timing()
+        r.reset_ray_count()
+        r.set_timing(True)
+        for _ in range(args.reps):
+            r.compute_frame(bounces)
+        r.synchronize()
+        r.set_timing(False)
+        ms, _ = r.dispatch_time_total()
+        rays = r.ray_count()
+        seg_t.zero_()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        for i in range(args.reps):
+            radiance(k0 + i)
+        t1.record(stream)
+        t1.synchronize()
+        segments = int(seg_t.item())
+        assert segments == rays, (segments, rays)
+        h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        h0.record(stream)
+        for _ in range(args.reps):
+            closest_hit()
+        h1.record(stream)
+        h1.synchronize()
+        frame_ms.append(ms / args.reps)
+        rad_ms.append(t0.elapsed_time(t1) / args.reps)
+        hit_ms.append(h0.elapsed_time(h1) / args.reps)
+        frame_rate.append(rays / ms / 1e3)
+        rad_rate.append(segments / t0.elapsed_time(t1) / 1e3)
+    med = statistics.median
+    emit(kind="radiance", bounces=bounces, rays=n, rounds=args.rounds, reps=args.reps,
+         segments_per_ray=round(rays / args.reps / n, 4), bit_identical_to_frame=same,
+         frame_ms=round(med(frame_ms), 4), frame_ms_min=round(min(frame_ms), 4), frame_ms_max=round(max(frame_ms), 4),
+         radiance_ms=round(med(rad_ms), 4), radiance_ms_min=round(min(rad_ms), 4), radiance_ms_max=round(max(rad_ms), 4),
+         frame_mray_s=round(med(frame_rate), 1), radiance_mray_s=round(med(rad_rate), 1),
+         ratio=round(med(rad_rate) / med(frame_rate), 3),
+         closest_hit_ms=round(med(hit_ms), 4), closest_hit_mray_s=round(n / med(hit_ms) / 1e3, 1),
+         closest_hit_ratio=round(n / med(hit_ms) / 1e3 / med(frame_rate), 3), build=r._lib.rt_build_hash().decode())
+
+
 def main():
     import torch
 
@@ -140,7 +237,12 @@ def main():
     ap.add_argument("--frames", type=int, default=32, help="frames of the render yardstick")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
-    ap.add_argument("--rounds", type=int, default=7, help="--occluded: rounds the series alternate over")
+    ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
+    ap.add_argument("--bounces", type=int, default=None, help="--radiance: bounce limit (default: the configuration's)")
+    ap.add_argument("--settle-ms", type=float, default=150.0, help="--radiance: untimed work before the rounds")
+    ap.add_argument("--rounds", type=int, default=7, help="--occluded, --radiance: rounds the series alternate over")
+    ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
+                    help="rt_set_tuning settings of the context (e.g. primary_pass=0: the yardstick frame without its pre-pass)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "query_bench needs a HIP device"
@@ -159,12 +261,17 @@ def main():
 
     def emit(**kw):
         rec = dict(config=args.config, width=args.width, height=args.height, **kw)
+        if tuning:
+            rec["tuning"] = tuning
         lines.append(rec)
         print(json.dumps(rec), flush=True)
 
     call = "rt_occluded_device" if args.occluded else "rt_trace_rays_device"
-    with Renderer(scene) as r:
-        if args.occluded and not args.sweep:
+    tuning = {k: int(v) for k, v in (kv.split("=", 1) for kv in args.tune)}
+    with Renderer(scene, tuning=tuning) as r:
+        if args.radiance:
+            radiance_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
+        elif args.occluded and not args.sweep:
             occlusion_bench(r, args, q, dev, emit)
         elif args.sweep:
             sizes = [s for s in (64, 256, 1024, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 1048576) if s < n] + [n]
