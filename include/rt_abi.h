@@ -49,7 +49,9 @@ extern "C" {
  * additive: occlusion queries (rt_occluded, rt_occluded_device, rt_occlusion_ray); 12,
  * additive: denoiser (rt_compute_features, rt_read_features, rt_features_device, rt_denoise,
  * rt_read_denoised, rt_copy_denoised_to_device, rt_denoise_params);
- * 12, additive: radiance queries (rt_radiance, rt_radiance_device, rt_radiance_ray). */
+ * 12, additive: radiance queries (rt_radiance, rt_radiance_device, rt_radiance_ray);
+ * 12, additive: temporal denoiser (rt_denoise_temporal, rt_temporal_reset, rt_read_temporal,
+ * rt_temporal_default_params, rt_temporal_params). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -623,6 +625,126 @@ RT_API int rt_features_device(rt_ctx* ctx, const void** normal_depth, const void
 RT_API int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
 RT_API int rt_read_denoised(rt_ctx* ctx, uint32_t* rgba8_out, float* rgba_f32_out);
 RT_API int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row);
+
+/* ---- temporal reprojection for the denoiser (ABI 12, additive: temporal denoiser) ----
+ *
+ * While the camera keeps moving, every displayed frame is a fresh 1-spp estimate. rt_denoise_temporal
+ * reprojects the previous call's blended result through the camera it was made with, validates it
+ * against geometry (hit flag, normal, world position), blends it with the new samples weighted by a
+ * per-pixel sample count, and then runs the a-trous filter with a colour tolerance that follows
+ * that count. The filtered result lands in the denoised buffers that already exist: rt_read_denoised
+ * and rt_copy_denoised_to_device serve it unchanged.
+ *
+ * STATE. Two history slots of three float4 planes each (96 B per pixel in all), allocated on the
+ * first call and freed by rt_destroy. A slot holds C (rgba), X (xyz, hit), Nn (normal.xyz, n), the
+ * matrix it was written with and a generation tag. The context keeps an accumulation generation G
+ * that rt_reset_accumulation increments; nothing else increments it. A call at generation G chooses
+ * the previous slot like this: if the current slot is valid and its tag is not G, the slots swap
+ * roles (the old current becomes previous); if the current slot is valid and its tag equals G,
+ * previous stays what it was (possibly none) and the current slot is overwritten. Within one
+ * accumulation generation the history is therefore always the last result of the generation before
+ * it -- the past is never counted twice -- and the growing accumulation outweighs it as N grows.
+ * rt_temporal_reset invalidates both slots: call it after material, texture or geometry edits,
+ * which reprojection cannot validate.
+ *
+ * world_to_pixel is the CURRENT camera's map from world space to pixel coordinates (pixel (x, y) is
+ * where the un-jittered ray of pixel (x, y) lands); it is stored with the slot and used by the next
+ * generation's call. It is an input to the contract, not part of it.
+ *
+ * THE TEMPORAL STAGE (rt_denoise_temporal; tests/temporal_ref.py restates it from here).
+ *
+ * Everything is f32, one IEEE operation per written operation, in the written order, with no
+ * contraction and correctly rounded division. W and H are (float)width and (float)height.
+ *
+ * Per pixel p = (x, y):
+ *
+ * 1. Current estimate.
+ *   c = accumulation(p) / D on all four channels;
+ *   N = (float)((k-1)*compute_per_frame), exactly the c0 and N of rt_denoise (D is N);
+ *   (o, d) is the pixel's un-jittered ray as rt_pick defines it;
+ *   n_p, t_p and hit_p come from the feature planes.
+ *
+ * 2. World point.
+ *   Hit: X_p = o + d*t_p per component (one multiply, one add), and wv = 1.
+ *   Miss: X_p = d, and wv = 0.
+ *
+ * 3. Projection through the previous slot's matrix M. This step runs only if a previous slot exists.
+ *   For rows i = 0, 1, 3: c_i = (M[i]*X.x + M[4+i]*X.y) + M[8+i]*X.z. On a hit, c_i = c_i + M[12+i] follows.
+ *   There is no history unless c_3 > 0.
+ *   fx = c_0/c_3 and fy = c_1/c_3.
+ *   There is no history unless fx > -1 && fx < W && fy > -1 && fy < H. Every one of these tests is false for NaN.
+ *
+ * 4. Bilinear taps.
+ *   x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0, bx = 1 - ax, by = 1 - ay.
+ *   The taps q, in this order:
+ *     (x0, y0) with w = bx*by;
+ *     (x0+1, y0) with w = ax*by;
+ *     (x0, y0+1) with w = bx*ay;
+ *     (x0+1, y0+1) with w = ax*ay.
+ *   A tap counts only if q is inside the image, w > 0, and hit_q == hit_p.
+ *   On a hit, two further tests apply:
+ *     the normal: (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z >= normal_min;
+ *     the position: e2 <= (sigma_position*sigma_position) * r2, with
+ *       e = X_p - X_q,
+ *       e2 = (e.x*e.x + e.y*e.y) + e.z*e.z,
+ *       f = X_p - o,
+ *       r2 = (f.x*f.x + f.y*f.y) + f.z*f.z.
+ *   Misses need nothing further.
+ *
+ * 5. History sums.
+ *   sw = sw + w, hc = hc + w*C_q (per channel) and hn = hn + w*n_q, in tap order starting from 0.
+ *   There is no history unless sw > 0.
+ *   Otherwise h = hc/sw and nh = min(hn/sw, (float)max_history).
+ *
+ * 6. Blend.
+ *   Without history: out = c and n_out = N.
+ *   With history: tot = nh + N, a = N/tot, out = h + (c - h)*a per channel, and n_out = tot.
+ *
+ * 7. Store. The current slot gets C = out, X = (X_p, hit_p) and Nn = (n_p, n_out). Its matrix becomes
+ *   params->world_to_pixel and its tag becomes G.
+ *
+ * 8. Filter. The a-trous iterations of rt_denoise run on c0 := out. The colour scale is per pixel:
+ *   s_i = sigma_color * 0.5f^i (exact scaling);
+ *   K_i = 1.0f/(s_i*s_i);
+ *   k_c(p) = n_out(p) * K_i, using the centre pixel's count.
+ *   Everything else is word for word the pass above. iterations == 0 gives out and its pack.
+ *
+ * Because k_c rounds differently (n_out*K_i here, 1/(s_i*s_i) with s0 = sigma_color/sqrtf(N) above), a
+ * call without history is close to rt_denoise of the same frame but is not promised bit-equal.
+ * End of the temporal contract.
+ *
+ * rt_denoise_temporal is an observation point exactly like rt_denoise: queued frames launch first,
+ * then the features are computed if stale, then the temporal stage runs, then the filter, all
+ * stream-ordered on rt_stream(ctx) and asynchronous. The accumulation, rt_read_output, k,
+ * rt_ray_count, the timing totals, the tile schedule, the feature planes and a later plain
+ * rt_denoise are all unaffected. denoise_params == NULL: rt_denoise_default_params.
+ * Errors: those of rt_denoise, plus RT_E_INVALID for a NULL rt_temporal_params (the matrix has no
+ * default), a non-finite matrix entry, max_history outside 1..65536, sigma_position not finite or
+ * <= 0, normal_min not finite or outside [-1, 1]. A failing call leaves the history as it was.
+ * rt_temporal_reset: drops all history; RT_OK when there is none.
+ * rt_read_temporal: synchronous; the pre-filter blend `out` (width*height*4 floats) and the per-pixel
+ *   history length n_out (width*height floats) of the last call; either pointer may be NULL.
+ *   RT_E_INVALID before any rt_denoise_temporal and after rt_temporal_reset. */
+typedef struct rt_temporal_params {
+    float world_to_pixel[16]; /* column-major 4x4, glam layout: the CURRENT camera's map from world space to
+                                 pixel coordinates; rows 0, 1, 3 give x*w, y*w, w; row 2 is ignored */
+    uint32_t max_history;     /* cap on the samples the past may weigh, 1..65536 */
+    float sigma_position;     /* relative world-space tolerance */
+    float normal_min;         /* minimum n_p . n_q, in [-1, 1] */
+    uint32_t _reserved;       /* 0 */
+} rt_temporal_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_temporal_params) == 80, "rt_temporal_params is 80 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_temporal_params) == 80, "rt_temporal_params is 80 bytes");
+#endif
+
+RT_API int rt_temporal_default_params(rt_temporal_params* out); /* matrix all zero, {32, 0.02f, 0.9f, 0} */
+RT_API int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* params,
+                               const rt_denoise_params* denoise_params /* NULL: defaults */);
+RT_API int rt_temporal_reset(rt_ctx* ctx);
+RT_API int rt_read_temporal(rt_ctx* ctx, float* rgba /* W*H*4 */, float* history /* W*H */);
 
 /* Readback (new: the reference only blits output_data to the swapchain,
  * src/renderer.rs:254-283). Synchronous; whole framebuffer, row-major

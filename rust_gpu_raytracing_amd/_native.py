@@ -105,7 +105,13 @@ class rt_denoise_params(ctypes.Structure):
                 ("sigma_albedo", ctypes.c_float), ("sigma_depth", ctypes.c_float)]
 
 
+class rt_temporal_params(ctypes.Structure):
+    _fields_ = [("world_to_pixel", ctypes.c_float * 16), ("max_history", ctypes.c_uint32),
+                ("sigma_position", ctypes.c_float), ("normal_min", ctypes.c_float), ("_reserved", ctypes.c_uint32)]
+
+
 assert ctypes.sizeof(rt_params) == 48
+assert ctypes.sizeof(rt_temporal_params) == 80
 assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
@@ -158,6 +164,10 @@ SIGNATURES = {
     "rt_denoise": (ctypes.c_int, [_P, ctypes.POINTER(rt_denoise_params)]),
     "rt_read_denoised": (ctypes.c_int, [_P, _P, _P]),
     "rt_copy_denoised_to_device": (ctypes.c_int, [_P, _P, _U32]),
+    "rt_temporal_default_params": (ctypes.c_int, [ctypes.POINTER(rt_temporal_params)]),
+    "rt_denoise_temporal": (ctypes.c_int, [_P, ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_denoise_params)]),
+    "rt_temporal_reset": (ctypes.c_int, [_P]),
+    "rt_read_temporal": (ctypes.c_int, [_P, _P, _P]),
     "rt_read_output_pitched": (ctypes.c_int, [_P, _P, _U32]),
     "rt_bytes_per_row": (_U32, [_U32, _U32]),
     "rt_ray_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),

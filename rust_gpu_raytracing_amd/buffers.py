@@ -120,11 +120,14 @@ RADIANCE_RAY = np.dtype([("origin", "<f4", 3), ("stream", "<u4"), ("direction", 
 # rt_denoise_params -- the guided a-trous filter (rt_denoise); defaults {4, 1.0, 0.1, 0.05}
 DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigma_albedo", "<f4"),
                            ("sigma_depth", "<f4")])
+# rt_temporal_params -- temporal reprojection (rt_denoise_temporal); defaults {0 matrix, 32, 0.02, 0.9, 0}
+TEMPORAL_PARAMS = np.dtype([("world_to_pixel", "<f4", 16), ("max_history", "<u4"), ("sigma_position", "<f4"),
+                            ("normal_min", "<f4"), ("_reserved", "<u4")])
 
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
-    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (DENOISE_PARAMS, 16),
+    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
 ):
     assert _dt.itemsize == _size, (_dt, _size)
 

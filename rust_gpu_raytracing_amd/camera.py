@@ -106,6 +106,24 @@ class Camera:
         rc["origin"] = self.position
         return rc
 
+    def world_to_pixel(self) -> np.ndarray:
+        """The column-major 4x4 (glam layout, (4 cols x 4) f32 like ``projection``) that maps a world
+        point to pixel coordinates: rows 0, 1, 3 give x*w, y*w, w, and pixel (x, y) is where the ray
+        ``recalculate_ray_directions`` gives pixel (x, y) lands. It inverts that function including
+        its two quirks -- x is scaled by f32(w)/f32(h) a second time before the inverse projection,
+        and a pixel's ray passes through x/w with no half-pixel offset:
+        x = (clip.x/aspect + clip.w) * w/2, y = (clip.y + clip.w) * h/2, clip = projection * view.
+        Computed in float64 and rounded once to f32 (rt_temporal_params.world_to_pixel)."""
+        w, h = self.viewport_width, self.viewport_height
+        pv = self.projection.astype(np.float64).T @ self.view.astype(np.float64).T  # row-major
+        aspect = float(f32(w) / f32(h))
+        m = np.empty((4, 4), np.float64)
+        m[0] = (pv[0] / aspect + pv[3]) * (w / 2.0)
+        m[1] = (pv[1] + pv[3]) * (h / 2.0)
+        m[2] = pv[2]
+        m[3] = pv[3]
+        return np.ascontiguousarray(m.T).astype(np.float32)
+
     def recalculate_ray_directions(self) -> np.ndarray:
         """src/camera.rs:139-182: one ``Ray`` per pixel, row-major (row 0 first)."""
         w, h = self.viewport_width, self.viewport_height

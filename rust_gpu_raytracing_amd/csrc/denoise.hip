@@ -1,5 +1,6 @@
-// denoise.hip -- first-hit feature buffers and the guided a-trous filter for gfx950
-// (rt_compute_features, rt_denoise).
+// denoise.hip -- first-hit feature buffers, the guided a-trous filter and its temporal
+// reprojection stage for gfx950 (rt_compute_features, rt_denoise, rt_denoise_temporal; DESIGN.md
+// §5.4d, §5.4f).
 //
 // FEATURES. Two float4 planes of width*height pixels, row-major:
 //   plane A: normal.xyz, t          plane B: albedo.rgb, hit (1.0f or 0.0f)
@@ -76,6 +77,78 @@
 // each texel then read from L2 once per workgroup instead of up to 25 times from the vector cache;
 // steps >= 4 load their taps directly (a tile + halo would be larger than the taps it serves).
 // Clamp and pack are fused into the last pass. No atomics; plain vector stores.
+//
+// THE TEMPORAL STAGE (rt_denoise_temporal; tests/temporal_ref.py restates it from here).
+//
+// Everything is f32, one IEEE operation per written operation, in the written order, with no
+// contraction and correctly rounded division. W and H are (float)width and (float)height.
+//
+// Per pixel p = (x, y):
+//
+// 1. Current estimate.
+//   c = accumulation(p) / D on all four channels;
+//   N = (float)((k-1)*compute_per_frame), exactly the c0 and N of rt_denoise (D is N);
+//   (o, d) is the pixel's un-jittered ray as rt_pick defines it;
+//   n_p, t_p and hit_p come from the feature planes.
+//
+// 2. World point.
+//   Hit: X_p = o + d*t_p per component (one multiply, one add), and wv = 1.
+//   Miss: X_p = d, and wv = 0.
+//
+// 3. Projection through the previous slot's matrix M. This step runs only if a previous slot exists.
+//   For rows i = 0, 1, 3: c_i = (M[i]*X.x + M[4+i]*X.y) + M[8+i]*X.z. On a hit, c_i = c_i + M[12+i] follows.
+//   There is no history unless c_3 > 0.
+//   fx = c_0/c_3 and fy = c_1/c_3.
+//   There is no history unless fx > -1 && fx < W && fy > -1 && fy < H. Every one of these tests is false for NaN.
+//
+// 4. Bilinear taps.
+//   x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0, bx = 1 - ax, by = 1 - ay.
+//   The taps q, in this order:
+//     (x0, y0) with w = bx*by;
+//     (x0+1, y0) with w = ax*by;
+//     (x0, y0+1) with w = bx*ay;
+//     (x0+1, y0+1) with w = ax*ay.
+//   A tap counts only if q is inside the image, w > 0, and hit_q == hit_p.
+//   On a hit, two further tests apply:
+//     the normal: (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z >= normal_min;
+//     the position: e2 <= (sigma_position*sigma_position) * r2, with
+//       e = X_p - X_q,
+//       e2 = (e.x*e.x + e.y*e.y) + e.z*e.z,
+//       f = X_p - o,
+//       r2 = (f.x*f.x + f.y*f.y) + f.z*f.z.
+//   Misses need nothing further.
+//
+// 5. History sums.
+//   sw = sw + w, hc = hc + w*C_q (per channel) and hn = hn + w*n_q, in tap order starting from 0.
+//   There is no history unless sw > 0.
+//   Otherwise h = hc/sw and nh = min(hn/sw, (float)max_history).
+//
+// 6. Blend.
+//   Without history: out = c and n_out = N.
+//   With history: tot = nh + N, a = N/tot, out = h + (c - h)*a per channel, and n_out = tot.
+//
+// 7. Store. The current slot gets C = out, X = (X_p, hit_p) and Nn = (n_p, n_out). Its matrix becomes
+//   params->world_to_pixel and its tag becomes G.
+//
+// 8. Filter. The a-trous iterations of rt_denoise run on c0 := out. The colour scale is per pixel:
+//   s_i = sigma_color * 0.5f^i (exact scaling);
+//   K_i = 1.0f/(s_i*s_i);
+//   k_c(p) = n_out(p) * K_i, using the centre pixel's count.
+//   Everything else is word for word the pass above. iterations == 0 gives out and its pack.
+//
+// Because k_c rounds differently (n_out*K_i here, 1/(s_i*s_i) with s0 = sigma_color/sqrtf(N) above), a
+// call without history is close to rt_denoise of the same frame but is not promised bit-equal.
+// End of the temporal contract.
+//
+// The temporal kernel: one pixel per lane over the same 32x8 tile, 256-thread workgroups. The camera
+// block of pixel_ray is read from the kernel arguments (scalar registers), so there is no LDS and no
+// barrier; the instance is chosen by where the camera ray comes from (ray buffer or matrices). Every
+// plane access is a 16-B vector load or store: 16 B of accumulation, 32 B of features (and 16 B of
+// ray buffer in that instance), then for a pixel that reprojects on screen 4 x 48 B gathered from
+// the previous slot -- neighbouring pixels reproject to neighbouring taps, so a wave's gathers
+// fall into a few rows -- and 48 B written to the current slot. The two slots are distinct buffers:
+// no hazard, no atomics. The four taps' loads are issued together (indices clamped into the image)
+// and the invalid ones dropped with selects, never multiplied by zero.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -170,6 +243,7 @@ struct DenoiseArgs {
     uint32_t width, height;
     uint32_t step;
     float k_a, k_c, sigma_depth;
+    const float4* __restrict__ nn;    // kPix (rt_denoise_temporal): the current slot's Nn plane, k_c(p) = nn(p).w * k_c
 };
 
 namespace {
@@ -180,7 +254,7 @@ struct Px {
 
 // The weight of tap q for centre p, without the kernel factor h[dy]*h[dx] (`hh`) folded in any
 // other order than the contract's: (((hh * g) * (ra*ra)) * (rc*rc)).
-__device__ __forceinline__ float tap_weight(const Px& p, const Px& q, float hh, const DenoiseArgs& a) {
+__device__ __forceinline__ float tap_weight(const Px& p, const Px& q, float hh, const DenoiseArgs& a, float k_c) {
     float g;
     const bool hp = p.ah.w != 0.0f, hq = q.ah.w != 0.0f;
     if (!hp && !hq) {
@@ -199,7 +273,7 @@ __device__ __forceinline__ float tap_weight(const Px& p, const Px& q, float hh, 
     const float xa = ((ar * ar + ag * ag) + ab * ab) * a.k_a;
     const float ra = 1.0f / (1.0f + xa);
     const float cr = p.c.x - q.c.x, cg = p.c.y - q.c.y, cb = p.c.z - q.c.z;
-    const float xc = ((cr * cr + cg * cg) + cb * cb) * a.k_c;
+    const float xc = ((cr * cr + cg * cg) + cb * cb) * k_c;
     const float rc = 1.0f / (1.0f + xc);
     return ((hh * g) * (ra * ra)) * (rc * rc);
 }
@@ -213,7 +287,8 @@ __device__ __forceinline__ void store_result(const DenoiseArgs& a, size_t idx, f
 }  // namespace
 
 // One a-trous iteration. kLds: the three planes' tile + halo (2*step pixels) staged in LDS.
-template <bool kLds>
+// kPix: the temporal filter's per-pixel colour scale (one extra scalar load at the centre pixel).
+template <bool kLds, bool kPix>
 __global__ void __launch_bounds__(kThreads) rt_denoise_pass_kernel(DenoiseArgs a) {
     extern __shared__ __attribute__((aligned(16))) float4 tile[];
     const uint32_t tid = threadIdx.x;
@@ -255,6 +330,8 @@ __global__ void __launch_bounds__(kThreads) rt_denoise_pass_kernel(DenoiseArgs a
         return q;
     };
     const Px p = load(x, y, 0, 0);
+    float k_c = a.k_c;
+    if constexpr (kPix) k_c = reinterpret_cast<const float*>(a.nn)[4u * idx + 3u] * a.k_c;
     const float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float4 num = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float den = 0.0f;
@@ -272,7 +349,7 @@ __global__ void __launch_bounds__(kThreads) rt_denoise_pass_kernel(DenoiseArgs a
                 const int qx = x + s * dx, qy = y + s * dy;
                 if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
                 const Px q = load(qx, qy, dx, dy);
-                wgt = tap_weight(p, q, hh, a);
+                wgt = tap_weight(p, q, hh, a, k_c);
                 if (!(wgt > 0.0f)) continue;
                 c = q.c;
             }
@@ -312,12 +389,179 @@ size_t rt_denoise_tile_bytes(uint32_t step) {
 
 hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
                                   uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
-                                  float sigma_depth, bool lds, hipStream_t stream) {
-    const DenoiseArgs a{nd, ah, src, dst, packed, width, height, step, k_a, k_c, sigma_depth};
+                                  float sigma_depth, bool lds, hipStream_t stream, const float4* nn) {
+    const DenoiseArgs a{nd, ah, src, dst, packed, width, height, step, k_a, k_c, sigma_depth, nn};
     const dim3 grid((width + kTileW - 1u) / kTileW, (height + kTileH - 1u) / kTileH);
-    if (lds && step <= 2u)
-        hipLaunchKernelGGL(rt_denoise_pass_kernel<true>, grid, dim3(kThreads), rt_denoise_tile_bytes(step), stream, a);
+    const bool tiled = lds && step <= 2u;
+    const size_t bytes = tiled ? rt_denoise_tile_bytes(step) : 0;
+    if (nn) {  // rt_denoise_temporal: k_c is K_i, scaled per pixel by nn(p).w
+        if (tiled)
+            hipLaunchKernelGGL((rt_denoise_pass_kernel<true, true>), grid, dim3(kThreads), bytes, stream, a);
+        else
+            hipLaunchKernelGGL((rt_denoise_pass_kernel<false, true>), grid, dim3(kThreads), bytes, stream, a);
+    } else if (tiled) {
+        hipLaunchKernelGGL((rt_denoise_pass_kernel<true, false>), grid, dim3(kThreads), bytes, stream, a);
+    } else {
+        hipLaunchKernelGGL((rt_denoise_pass_kernel<false, false>), grid, dim3(kThreads), bytes, stream, a);
+    }
+    return hipGetLastError();
+}
+
+// ---- the temporal stage --------------------------------------------------------------------------
+
+struct TemporalArgs {
+    const float4* __restrict__ accum;
+    const float4* __restrict__ nd;      // plane A: normal.xyz, t
+    const float4* __restrict__ ah;      // plane B: albedo.rgb, hit
+    const float4* __restrict__ prev_c;  // the previous slot's planes; null: there is none
+    const float4* __restrict__ prev_x;
+    const float4* __restrict__ prev_nn;
+    float4* __restrict__ cur_c;         // the current slot's planes
+    float4* __restrict__ cur_x;
+    float4* __restrict__ cur_nn;
+    float4* __restrict__ dn;            // iterations == 0: `out` and its pack as the denoised result; else null
+    uint32_t* __restrict__ packed;
+    float m[16];                        // the previous slot's world_to_pixel
+    float n;                            // N = D
+    float max_history, sigma2, normal_min;  // (float)max_history, sigma_position*sigma_position
+};
+
+// Steps 1-7 of the temporal contract. kGen: the camera ray is computed from the matrices
+// (rt_update_camera_matrices in effect); else it is read from the ray buffer.
+template <bool kGen>
+__global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, TemporalArgs t) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t x = blockIdx.x * kTileW + (tid & (kTileW - 1u)), y = blockIdx.y * kTileH + tid / kTileW;
+    if (x >= ka.width || y >= ka.height) return;
+    const int w = (int)ka.width, h = (int)ka.height;
+    const size_t idx = (size_t)y * ka.width + (size_t)x;
+    // 1. current estimate
+    const float4 acc = ld_f4(t.accum, idx);
+    const float4 c = make_float4(acc.x / t.n, acc.y / t.n, acc.z / t.n, acc.w / t.n);
+    const float4 nd = ld_f4(t.nd, idx);
+    const float hit_p = ld_f4(t.ah, idx).w;
+    const bool hit = hit_p != 0.0f;
+    f3 d;
+    if constexpr (kGen) {
+        float cam[33];  // constant indices into the kernel arguments: scalar registers, not scratch
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            cam[i] = ka.inv_proj[i];
+            cam[16 + i] = ka.inv_view[i];
+        }
+        cam[32] = ka.aspect;
+        d = camera_ray(ka, cam, x, y);
+    } else {
+        const float4 cr = ld_f4(ka.camera_rays, idx);
+        d = mk(cr.x, cr.y, cr.z);
+    }
+    const f3 o = mk(ka.camera_origin[0], ka.camera_origin[1], ka.camera_origin[2]);
+    // 2. world point
+    const f3 xp = hit ? mk(o.x + d.x * nd.w, o.y + d.y * nd.w, o.z + d.z * nd.w) : d;
+    float4 out = c;
+    float n_out = t.n;
+    if (t.prev_c) {
+        // 3. projection
+        float c0 = (t.m[0] * xp.x + t.m[4] * xp.y) + t.m[8] * xp.z;
+        float c1 = (t.m[1] * xp.x + t.m[5] * xp.y) + t.m[9] * xp.z;
+        float c3 = (t.m[3] * xp.x + t.m[7] * xp.y) + t.m[11] * xp.z;
+        if (hit) {
+            c0 = c0 + t.m[12];
+            c1 = c1 + t.m[13];
+            c3 = c3 + t.m[15];
+        }
+        const float fx = c0 / c3, fy = c1 / c3;
+        if (c3 > 0.0f && fx > -1.0f && fx < (float)w && fy > -1.0f && fy < (float)h) {
+            // 4. bilinear taps: fx in (-1, W) puts x0 in [-1, W-1]; indices are clamped into the
+            // image so that all loads can be issued, and `inside` drops the clamped ones
+            const float x0 = __builtin_floorf(fx), y0 = __builtin_floorf(fy);
+            const float ax = fx - x0, ay = fy - y0, bx = 1.0f - ax, by = 1.0f - ay;
+            const int ix = (int)x0, iy = (int)y0;
+            const float wt[4] = {bx * by, ax * by, bx * ay, ax * ay};
+            float4 qc[4], qx[4], qn[4];
+            bool inside[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int qxi = ix + (k & 1), qyi = iy + (k >> 1);
+                inside[k] = qxi >= 0 && qxi < w && qyi >= 0 && qyi < h;
+                const int cx = min(max(qxi, 0), w - 1), cy = min(max(qyi, 0), h - 1);
+                const size_t qi = (size_t)cy * ka.width + (size_t)cx;
+                qc[k] = ld_f4(t.prev_c, qi);
+                qx[k] = ld_f4(t.prev_x, qi);
+                qn[k] = ld_f4(t.prev_nn, qi);
+            }
+            const float fx_ = xp.x - o.x, fy_ = xp.y - o.y, fz_ = xp.z - o.z;
+            const float r2 = (fx_ * fx_ + fy_ * fy_) + fz_ * fz_;
+            const float lim = t.sigma2 * r2;
+            float sw = 0.0f, hn = 0.0f;
+            float4 hc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                bool ok = inside[k] && wt[k] > 0.0f && qx[k].w == hit_p;
+                if (hit) {
+                    const float dn = (nd.x * qn[k].x + nd.y * qn[k].y) + nd.z * qn[k].z;
+                    const float ex = xp.x - qx[k].x, ey = xp.y - qx[k].y, ez = xp.z - qx[k].z;
+                    const float e2 = (ex * ex + ey * ey) + ez * ez;
+                    ok = ok && dn >= t.normal_min && e2 <= lim;
+                }
+                // 5. history sums
+                sw = ok ? sw + wt[k] : sw;
+                hc.x = ok ? hc.x + wt[k] * qc[k].x : hc.x;
+                hc.y = ok ? hc.y + wt[k] * qc[k].y : hc.y;
+                hc.z = ok ? hc.z + wt[k] * qc[k].z : hc.z;
+                hc.w = ok ? hc.w + wt[k] * qc[k].w : hc.w;
+                hn = ok ? hn + wt[k] * qn[k].w : hn;
+            }
+            if (sw > 0.0f) {
+                // 6. blend
+                const float4 hh = make_float4(hc.x / sw, hc.y / sw, hc.z / sw, hc.w / sw);
+                const float nq = hn / sw;
+                const float nh = nq < t.max_history ? nq : t.max_history;
+                const float tot = nh + t.n;
+                const float a = t.n / tot;
+                out = make_float4(hh.x + (c.x - hh.x) * a, hh.y + (c.y - hh.y) * a, hh.z + (c.z - hh.z) * a,
+                                  hh.w + (c.w - hh.w) * a);
+                n_out = tot;
+            }
+        }
+    }
+    // 7. store
+    t.cur_c[idx] = out;
+    t.cur_x[idx] = make_float4(xp.x, xp.y, xp.z, hit_p);
+    t.cur_nn[idx] = make_float4(nd.x, nd.y, nd.z, n_out);
+    if (t.dn) {
+        t.dn[idx] = out;
+        t.packed[idx] = pack_rgba8(clamp01(out.x), clamp01(out.y), clamp01(out.z), clamp01(out.w));
+    }
+}
+
+hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
+                              float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
+                              uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
+                              hipStream_t stream) {
+    TemporalArgs t{};
+    t.accum = accum;
+    t.nd = nd;
+    t.ah = ah;
+    if (prev) {
+        t.prev_c = prev[0];
+        t.prev_x = prev[1];
+        t.prev_nn = prev[2];
+        for (int i = 0; i < 16; ++i) t.m[i] = prev_matrix[i];
+    }
+    t.cur_c = cur[0];
+    t.cur_x = cur[1];
+    t.cur_nn = cur[2];
+    t.dn = dn;
+    t.packed = packed;
+    t.n = n;
+    t.max_history = max_history;
+    t.sigma2 = sigma2;
+    t.normal_min = normal_min;
+    const dim3 grid((ka.width + kTileW - 1u) / kTileW, (ka.height + kTileH - 1u) / kTileH);
+    if (ka.gen_rays)
+        hipLaunchKernelGGL(rt_temporal_kernel<true>, grid, dim3(kThreads), 0, stream, ka, t);
     else
-        hipLaunchKernelGGL(rt_denoise_pass_kernel<false>, grid, dim3(kThreads), 0, stream, a);
+        hipLaunchKernelGGL(rt_temporal_kernel<false>, grid, dim3(kThreads), 0, stream, ka, t);
     return hipGetLastError();
 }

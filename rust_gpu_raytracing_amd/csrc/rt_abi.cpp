@@ -77,7 +77,11 @@ hipError_t rt_launch_denoise_init(const float4* accum, float4* dst, uint32_t* pa
                                   hipStream_t stream);
 hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
                                   uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
-                                  float sigma_depth, bool lds, hipStream_t stream);
+                                  float sigma_depth, bool lds, hipStream_t stream, const float4* nn = nullptr);
+hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
+                              float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
+                              uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
+                              hipStream_t stream);
 hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
                              uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
                              uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
@@ -101,6 +105,7 @@ static_assert(sizeof(rt_sub_object_info) == 32, "SubObjectInfo is 32 bytes");
 static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
 static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
+static_assert(sizeof(rt_temporal_params) == 80, "rt_temporal_params is 80 bytes");
 static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
 static_assert(sizeof(rt_radiance_ray) == sizeof(rt_query_ray), "rt_radiance_ray is an rt_query_ray with the stream for _pad0");
 static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ray, direction) == 16,
@@ -435,6 +440,18 @@ struct rt_ctx {
     uint32_t* d_dn_out = nullptr;                 // the packed denoised output
     int dn_result = -1;                           // which of d_dn holds the last rt_denoise's result; -1: none yet
     bool denoise_lds = true;                      // tuning "denoise_lds" 0: the passes with step 1, 2 load directly
+    // temporal reprojection (rt_denoise_temporal): two history slots of three float4 planes (C: rgba;
+    // X: xyz, hit; Nn: normal.xyz, n), each with the world_to_pixel matrix it was written with and
+    // the accumulation generation it was written in. accum_gen counts rt_reset_accumulation calls.
+    struct TemporalSlot {
+        float4* plane[3] = {};
+        float matrix[16] = {};
+        uint64_t gen = 0;
+        bool valid = false;
+    } t_slot[2];
+    int t_cur = 0;            // the slot the last rt_denoise_temporal wrote (when valid)
+    int t_prev = -1;          // the slot it read; -1: none
+    uint64_t accum_gen = 0;   // G
 
     std::string err;
 };
@@ -904,7 +921,9 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
                     ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
-                    ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out};
+                    ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out,
+                    ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
+                    ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2]};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -1020,6 +1039,7 @@ int rt_reset_accumulation(rt_ctx* ctx, const rt_params* params) {
     RT_HIP(ctx, hipMemsetAsync(ctx->d_accum, 0, ctx->n_pixels * 16, ctx->stream));
     ctx->params = *params;
     ctx->k = params->accumulation_index;
+    ++ctx->accum_gen;  // rt_denoise_temporal: a new accumulation generation
     return RT_OK;
 }
 
@@ -2124,6 +2144,116 @@ int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per
         return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: bytes_per_row < 4 * width");
     RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_dn_out, 4u * (size_t)ctx->width,
                                  4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+// ---- temporal reprojection (denoise.hip) --------------------------------------------------------
+int rt_temporal_default_params(rt_temporal_params* out) {
+    if (!out) return RT_E_INVALID;
+    *out = rt_temporal_params{};
+    out->max_history = 32u;
+    out->sigma_position = 0.02f;
+    out->normal_min = 0.9f;
+    return RT_OK;
+}
+
+int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt_denoise_params* params) {
+    RT_ENTER(ctx);  // an observation point: the queued frames are launched first
+    rt_denoise_params dp;
+    (void)rt_denoise_default_params(&dp);
+    if (params) dp = *params;
+    if (ctx->world > 1)
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: a rank context (world_size > 1) has no full frame");
+    if (ctx->params.accumulate != 1u)
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: Params.accumulate != 1 never writes the accumulation");
+    if (ctx->k - 1u == 0u || (ctx->k - 1u) * ctx->params.compute_per_frame == 0u)  // D would be 0
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: no frame since the last reset");
+    if (dp.iterations > kMaxDenoiseIterations)
+        return fail(ctx, RT_E_INVALID,
+                    "rt_denoise_temporal: iterations must be <= " + std::to_string(kMaxDenoiseIterations));
+    for (float sgm : {dp.sigma_color, dp.sigma_albedo, dp.sigma_depth})
+        if (!std::isfinite(sgm) || !(sgm > 0.0f))
+            return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: every sigma must be finite and > 0");
+    if (!tparams) return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: rt_temporal_params is NULL (the matrix has no default)");
+    const rt_temporal_params tp = *tparams;
+    for (float m : tp.world_to_pixel)
+        if (!std::isfinite(m)) return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: world_to_pixel is not finite");
+    if (tp.max_history < 1u || tp.max_history > 65536u)
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: max_history must be in 1..65536");
+    if (!std::isfinite(tp.sigma_position) || !(tp.sigma_position > 0.0f))
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: sigma_position must be finite and > 0");
+    if (!std::isfinite(tp.normal_min) || tp.normal_min < -1.0f || tp.normal_min > 1.0f)
+        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: normal_min must be in [-1, 1]");
+    int rc = build_features(ctx);
+    if (rc) return rc;
+    for (float4*& plane : ctx->d_dn)
+        if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    if (!ctx->d_dn_out && (rc = dev_alloc(ctx, &ctx->d_dn_out, ctx->n_pixels))) return rc;
+    for (rt_ctx::TemporalSlot& slot : ctx->t_slot)
+        for (float4*& plane : slot.plane)
+            if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    // the slot rule: within one accumulation generation the history stays the last result of the
+    // generation before it, so the past is never counted twice
+    int cur = ctx->t_cur, prev = ctx->t_prev;
+    if (ctx->t_slot[cur].valid && ctx->t_slot[cur].gen != ctx->accum_gen) {
+        prev = cur;
+        cur ^= 1;
+    } else if (!ctx->t_slot[cur].valid) {
+        prev = -1;
+    }
+    const bool has_prev = prev >= 0 && ctx->t_slot[prev].valid;
+    rt_ctx::TemporalSlot& sc = ctx->t_slot[cur];
+    const uint32_t n_samples = (ctx->k - 1u) * ctx->params.compute_per_frame;
+    KernelArgs kb{};
+    scene_base_args(ctx, kb);
+    kb.camera_rays = ctx->d_rays;
+    const bool zero = dp.iterations == 0;
+    RT_HIP(ctx, rt_launch_temporal(kb, ctx->d_accum, ctx->d_feat[0], ctx->d_feat[1],
+                                   has_prev ? ctx->t_slot[prev].plane : nullptr, sc.plane,
+                                   has_prev ? ctx->t_slot[prev].matrix : nullptr, zero ? ctx->d_dn[0] : nullptr,
+                                   zero ? ctx->d_dn_out : nullptr, (float)n_samples, (float)tp.max_history,
+                                   tp.sigma_position * tp.sigma_position, tp.normal_min, ctx->stream));
+    // the current slot is being rewritten from here on: the bookkeeping follows the launch
+    std::memcpy(sc.matrix, tp.world_to_pixel, sizeof(sc.matrix));
+    sc.gen = ctx->accum_gen;
+    sc.valid = true;
+    ctx->t_cur = cur;
+    ctx->t_prev = has_prev ? prev : -1;
+    const float k_a = 1.0f / (dp.sigma_albedo * dp.sigma_albedo);
+    float scale = 1.0f;
+    for (uint32_t i = 0; i < dp.iterations; i++, scale *= 0.5f) {
+        const float s_i = dp.sigma_color * scale;
+        const float k_i = 1.0f / (s_i * s_i);
+        const bool last = i + 1 == dp.iterations;
+        RT_HIP(ctx, rt_launch_denoise_pass(ctx->d_feat[0], ctx->d_feat[1], i == 0 ? sc.plane[0] : ctx->d_dn[(i - 1u) & 1u],
+                                           ctx->d_dn[i & 1u], last ? ctx->d_dn_out : nullptr, ctx->width, ctx->height,
+                                           1u << i, k_a, k_i, dp.sigma_depth, ctx->denoise_lds, ctx->stream,
+                                           sc.plane[2]));
+    }
+    ctx->dn_result = zero ? 0 : (int)((dp.iterations - 1u) & 1u);
+    return RT_OK;
+}
+
+int rt_temporal_reset(rt_ctx* ctx) {
+    RT_ENTER_NOFLUSH(ctx);
+    for (rt_ctx::TemporalSlot& slot : ctx->t_slot) slot.valid = false;
+    ctx->t_prev = -1;
+    return RT_OK;
+}
+
+int rt_read_temporal(rt_ctx* ctx, float* rgba, float* history) {
+    RT_ENTER_NOFLUSH(ctx);
+    const rt_ctx::TemporalSlot& slot = ctx->t_slot[ctx->t_cur];
+    if (!slot.valid) return fail(ctx, RT_E_INVALID, "rt_read_temporal: no rt_denoise_temporal since the last reset");
+    if (rgba) RT_HIP(ctx, hipMemcpyAsync(rgba, slot.plane[0], ctx->n_pixels * 16, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> nn;
+    if (history) {
+        nn.resize((size_t)ctx->n_pixels * 4);
+        RT_HIP(ctx, hipMemcpyAsync(nn.data(), slot.plane[2], ctx->n_pixels * 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (history)
+        for (size_t i = 0; i < (size_t)ctx->n_pixels; i++) history[i] = nn[4 * i + 3];
     return RT_OK;
 }
 

@@ -480,6 +480,42 @@ class Renderer:
         self._call("rt_features_device", ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
 
+    def denoise_temporal(self, world_to_pixel, max_history=None, sigma_position=None, normal_min=None,
+                         **denoise_kwargs):
+        """Temporal reprojection, then the guided a-trous filter (rt_denoise_temporal; the contract
+        is in include/rt_abi.h). ``world_to_pixel`` is the current camera's column-major 4x4
+        (``Camera.world_to_pixel()``); arguments left None take rt_temporal_default_params and
+        ``denoise_kwargs`` are ``denoise``'s. Returns (rgba_f32 (H, W, 4), rgba8 (H, W) uint32)."""
+        t = N.rt_temporal_params()
+        N.check(None, self._lib.rt_temporal_default_params(ctypes.byref(t)), self._lib)
+        t.world_to_pixel[:] = [float(v) for v in np.asarray(world_to_pixel, np.float32).reshape(16)]
+        for key, value in (("max_history", max_history), ("sigma_position", sigma_position),
+                           ("normal_min", normal_min)):
+            if value is not None:
+                setattr(t, key, value)
+        p = N.rt_denoise_params()
+        N.check(None, self._lib.rt_denoise_default_params(ctypes.byref(p)), self._lib)
+        for key, value in denoise_kwargs.items():
+            if key not in ("iterations", "sigma_color", "sigma_albedo", "sigma_depth"):
+                raise TypeError(f"denoise_temporal() got an unexpected keyword argument {key!r}")
+            if value is not None:
+                setattr(p, key, value)
+        self._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
+        return self.read_denoised()
+
+    def temporal_reset(self) -> None:
+        """Drop all reprojection history (rt_temporal_reset): after material, texture or geometry
+        edits, which reprojection cannot validate."""
+        self._call("rt_temporal_reset")
+
+    def read_temporal(self):
+        """(rgba_f32 (H, W, 4) pre-filter blend, history (H, W) float32 per-pixel sample count) of
+        the last ``denoise_temporal`` (rt_read_temporal)."""
+        f = np.zeros((self.height, self.width, 4), np.float32)
+        n = np.zeros((self.height, self.width), np.float32)
+        self._call("rt_read_temporal", N.ptr(f), N.ptr(n))
+        return f, n
+
     def denoise(self, iterations=None, sigma_color=None, sigma_albedo=None, sigma_depth=None):
         """The guided a-trous filter over the accumulated frame (rt_denoise; the contract is in
         include/rt_abi.h): an observation point that changes nothing a render reads. Arguments left

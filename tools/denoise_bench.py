@@ -11,7 +11,14 @@ Per configuration, after `--frames` rendered frames and a warm-up of every serie
 * ms per rt_denoise with iterations = 0..5, the step-1 and step-2 passes LDS-tiled (tuning
   "denoise_lds" 1) and with direct loads (0); the time of the pass with step 2^i is the difference
   t(i+1) - t(i) of the medians (the clamp-and-pack moves from one pass to the next, so it cancels);
-* ms per whole default rt_denoise (4 iterations), both ways.
+* ms per whole default rt_denoise (4 iterations), both ways;
+* ms per rt_denoise_temporal with iterations = 0 (the temporal stage alone, plus the 20 B per pixel of
+  its result and pack) and with the default iterations, without a previous slot (rt_temporal_reset,
+  a host-only call, before each call) and with one (before each timed round: a call, a reset of the
+  accumulation, the same frames again and one untimed call; every timed call then reprojects the
+  same previous slot). The stage is quoted against its one-touch floor of 144 B per pixel (16 B of
+  accumulation, 32 B of features, 48 B of history read once, 48 B written) and the whole call
+  against the default rt_denoise of the same job.
 
 Timing: device events on the context's stream around `--reps` stream-ordered calls; the series
 alternate over `--rounds` rounds (an A/B in one process, same clocks); median, minimum and maximum
@@ -37,6 +44,7 @@ from rust_gpu_raytracing_amd.scene import build_config  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # bench.py: MI355X HBM3E peak
 PASS_BYTES_PER_PIXEL = 48 + 16
+TEMPORAL_BYTES_PER_PIXEL = 16 + 32 + 48 + 48
 MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16
 
 
@@ -61,7 +69,8 @@ def main():
             if line.startswith("{") and "ms_per_step" in line:
                 frame_ms = float(json.loads(line)["ms_per_step"])
     record = dict(width=args.width, height=args.height, reps=args.reps, rounds=args.rounds, frames=args.frames,
-                  hbm_peak_gbs=HBM_PEAK_GBS, pass_bytes_per_pixel=PASS_BYTES_PER_PIXEL, c2_frame_ms=frame_ms,
+                  hbm_peak_gbs=HBM_PEAK_GBS, pass_bytes_per_pixel=PASS_BYTES_PER_PIXEL,
+                  temporal_bytes_per_pixel=TEMPORAL_BYTES_PER_PIXEL, c2_frame_ms=frame_ms,
                   device=torch.cuda.get_device_name(0), configs={})
     for config in args.configs:
         scene, bounces = build_config(config, width=args.width, height=args.height)
@@ -83,14 +92,45 @@ def main():
                 p.iterations = iterations
                 return lambda: r._call("rt_denoise", ctypes.byref(p))
 
-            series = {"features": (None, features)}
+            def temporal(iterations, previous):
+                t = N.rt_temporal_params()
+                r._lib.rt_temporal_default_params(ctypes.byref(t))
+                t.world_to_pixel[:] = [float(v) for v in scene.camera.world_to_pixel().reshape(16)]
+                p = N.rt_denoise_params()
+                r._lib.rt_denoise_default_params(ctypes.byref(p))
+                p.iterations = iterations
+
+                def call():
+                    if not previous:
+                        r._call("rt_temporal_reset")
+                    r._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
+
+                def setup():  # a previous slot from the generation before, the same accumulation again
+                    r._call("rt_temporal_reset")
+                    r._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
+                    r.reset_accumulation()
+                    for _ in range(args.frames):
+                        r.compute_frame(bounces)
+                    r._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
+                    r.synchronize()
+
+                return call, (setup if previous else None)
+
+            series = {"features": (None, features, None)}
             for lds in (1, 0):
                 for it in range(MAX_ITERATIONS + 1):
-                    series[f"denoise_it{it}/lds{lds}"] = (lds, denoise(it))
+                    series[f"denoise_it{it}/lds{lds}"] = (lds, denoise(it), None)
+            for it in (0, 4):
+                for previous in (0, 1):
+                    series[f"temporal_it{it}/prev{previous}"] = (None, *temporal(it, previous))
             results = {}
-            for name, (lds, fn) in series.items():  # warm-up of everything timed; the variants agree
+            for name, (lds, fn, setup) in series.items():  # warm-up of everything timed; the variants agree
                 if lds is not None:
                     r.set_tuning("denoise_lds", lds)
+                elif name.startswith("temporal"):
+                    r.set_tuning("denoise_lds", 1)
+                if setup:
+                    setup()
                 fn()
                 r.synchronize()
                 if lds is not None:
@@ -101,9 +141,13 @@ def main():
                     results[key] = (f.tobytes(), u.tobytes())
             ms = {k: [] for k in series}
             for _ in range(args.rounds):
-                for name, (lds, fn) in series.items():
+                for name, (lds, fn, setup) in series.items():
                     if lds is not None:
                         r.set_tuning("denoise_lds", lds)
+                    elif name.startswith("temporal"):
+                        r.set_tuning("denoise_lds", 1)
+                    if setup:
+                        setup()
                     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     t0.record(stream)
                     for _ in range(args.reps):
@@ -130,6 +174,14 @@ def main():
                 rec[f"lds{lds}"] = dict(
                     denoise_by_iterations={f"it{it}": stat(ms[f"denoise_it{it}/lds{lds}"]) for it in range(MAX_ITERATIONS + 1)},
                     passes=passes, default_denoise=stat(ms[f"denoise_it4/lds{lds}"]))
+            t_floor = args.width * args.height * TEMPORAL_BYTES_PER_PIXEL / (HBM_PEAK_GBS * 1e9) * 1e3
+            plain = float(np.median(ms["denoise_it4/lds1"]))
+            rec["temporal"] = dict(traffic_floor_ms_stage=round(t_floor, 5))
+            for previous in (0, 1):
+                stage, whole = stat(ms[f"temporal_it0/prev{previous}"]), stat(ms[f"temporal_it4/prev{previous}"])
+                stage["floor_multiple"] = round(stage["ms"] / t_floor, 3)
+                whole["of_default_denoise"] = round(whole["ms"] / plain, 4)
+                rec["temporal"][f"prev{previous}"] = dict(stage_it0=stage, default_it4=whole)
             record["configs"][config] = rec
             print(json.dumps({config: rec}), flush=True)
     out = Path(args.out)
