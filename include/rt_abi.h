@@ -51,7 +51,8 @@ extern "C" {
  * rt_read_denoised, rt_copy_denoised_to_device, rt_denoise_params);
  * 12, additive: radiance queries (rt_radiance, rt_radiance_device, rt_radiance_ray);
  * 12, additive: temporal denoiser (rt_denoise_temporal, rt_temporal_reset, rt_read_temporal,
- * rt_temporal_default_params, rt_temporal_params). */
+ * rt_temporal_default_params, rt_temporal_params);
+ * 12, additive: gather queries (rt_gather, rt_gather_device, rt_gather_point). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -506,6 +507,103 @@ RT_API int rt_radiance_device(rt_ctx* ctx, const void* rays_device, void* radian
                               uint32_t bounces, uint32_t first_sample, uint32_t samples,
                               void* segments_device /* may be NULL; one u64, added to */);
 
+/* ---- gather queries (ABI 12, additive: gather queries) ----------------------
+ *
+ * "How much light does this surface point gather?": per point, the summed light of `samples`
+ * paths that leave the point through the renderer's own diffuse lobe. Irradiance probes and
+ * lightmap texels: a few thousand to a million points with hundreds of hemisphere samples
+ * each. The directions are drawn on the device with the reference's RNG, the samples of a point
+ * are spread over the lanes of the device, and the reduction order is stated, so every value is
+ * bit-exact and independent of placement and schedule.
+ *
+ * What comes back is what a roughness-1, non-specular, non-glass surface at the point would
+ * gather in per_pixel (compute_shader.wgsl:210-314): the scatter direction there,
+ * specular + (diffuse - specular) * roughness, is at roughness 1 the diffuse lobe's draw
+ * normalize(n + (gx, gy, gz)) that step 2 below makes, to within the two roundings of that
+ * lerp. A bake therefore matches the frames the same library renders. */
+
+/* {position, stream}, {normal, pad}: the layout of rt_radiance_ray. 32 bytes. */
+typedef struct rt_gather_point {
+    float position[3];
+    uint32_t stream;  /* takes the place of the pixel index in the seeds; use streams >= 1 */
+    float normal[3];  /* used as given: not normalised */
+    float _pad1;      /* ignored */
+} rt_gather_point;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
+#endif
+
+/* Writes four floats per point, in order; nothing outside [0, 4 * count) is written.
+ *
+ * THE GATHER CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+ * written order, with no contraction. For point i with record (x, stream, n):
+ *  1. Sample index and origin. For s = 0 .. samples-1, u = first_sample + s (u32, wrapping).
+ *     o = x + n * 0.0001f per component: one multiply and one add (the reference's bounce
+ *     offset, as restated at oracle/pathtrace_oracle.c:511).
+ *  2. Direction. dseed = (stream * u * 326624u) ^ 0x9E3779B9u (u32, wrapping).
+ *     gx, gy, gz = normal_distribution(&dseed) three times, in that order
+ *     (compute_shader.wgsl:622-628, theta drawn before rho).
+ *     dir = normalize(n + (gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and
+ *     dot(v, v) = (x*x + y*y) + z*z. n is used as given and is not normalised.
+ *  3. Path. L_s is the result rt_radiance defines for the record (o, stream, dir) with
+ *     first_sample = u, samples = 1 and the call's bounces: per_pixel with its own seed
+ *     stream * u * 326624u, its own jitter, and everything else of a frame.
+ *  4. Reduction. P_j (j = 0 .. 63) starts at +0.0f on all four channels. For s ascending,
+ *     P_{s mod 64} = P_{s mod 64} + L_s. Then, for off = 32, 16, 8, 4, 2, 1:
+ *     P_j = P_j + P_{j+off} for every j < off. radiance[i] = P_0. Lanes that got no sample
+ *     take part with +0.0f. (An xor butterfly gives the same bits on finite values, because
+ *     f32 addition commutes.)
+ * End of the gather contract.
+ *
+ * Consequences:
+ *  - The caller divides by `samples`. Nothing is clamped or packed.
+ *  - bounces == 0 gives all-zero radiance and no segments, and is RT_OK. samples == 0 is
+ *    RT_E_INVALID (whatever `count` is).
+ *  - Stream 0 makes both seeds constant, so it draws the same sample every time, as pixel 0
+ *    does in the reference: callers use streams >= 1.
+ *  - A draw of exactly 0 makes rho infinite, as in the reference; the result is then
+ *    unspecified.
+ *  - Exactness holds for the domain of the radiance queries, for every segment of a path
+ *    (position and normal are such that o and dir are in it). Termination is theirs too: a lane
+ *    runs at most ceil(samples / 64) * bounces walks per (point, stripe) it takes.
+ *  - *segments receives the call's counted ray segments under the rule of rt_radiance: every
+ *    trace_ray call is counted, and a path that escapes stops counting. In the device variant
+ *    the kernel adds the total into the caller's u64 (it is added to, not set: one reduction
+ *    and one atomic add per wave at exit).
+ *
+ * Scene visibility and side effects are those of rt_trace_rays: the query sees the scene as
+ * of the call -- materials, textures and the environment map now matter too -- with the
+ * accelerators prepared exactly as a dispatch prepares them, and changes nothing a render can
+ * observe (queued frames stay queued; the accumulation, the output, the accumulation index,
+ * rt_ray_count, the timing totals, the tile schedule, the feature planes and the denoiser's
+ * buffers are untouched). The result does not depend on the brute-force mode, on any
+ * rt_set_tuning key or on triangle pruning modes 0 and 1 (mode 2 is inexact here as for
+ * frames and ray queries). It works on rank contexts (world_size > 1) as the other queries do.
+ *
+ * Both entry points run in launches of at most tuning "gather_chunk" points: the partials
+ * P_j of a launch live in a buffer the context owns, 1 KB per point (16 MB at the default),
+ * allocated on first use and freed by rt_destroy.
+ * rt_gather: host pointers, synchronous. Staged through the pinned buffer of rt_trace_rays
+ * in chunks of tuning "query_chunk" points (32 bytes in, 16 bytes out per point). `segments`
+ * may be NULL.
+ * rt_gather_device: device pointers on the context's device; points and radiance 16-byte
+ * aligned, segments_device (may be NULL) 8-byte aligned; stream-ordered on rt_stream(ctx), no
+ * host copy, asynchronous. RT_E_INVALID when any of them is not device memory of the context's
+ * device, as for rt_trace_rays_device.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries; by default
+ * calls of fewer than 262144 walks (count * samples) read the scene from global memory.
+ * count == 0 returns RT_OK and launches nothing; a NULL points or radiance pointer with
+ * count > 0 is RT_E_INVALID. */
+RT_API int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance /* 4 floats per point */,
+                     uint64_t count, uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                     uint64_t* segments /* may be NULL */);
+RT_API int rt_gather_device(rt_ctx* ctx, const void* points_device, void* radiance_device, uint64_t count,
+                            uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                            void* segments_device /* may be NULL; one u64, added to */);
+
 /* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
  *
  * What an interactive host shows right after the camera or the scene moved: the reference resets
@@ -837,7 +935,8 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "primary_waves" 8|0, "primary_tile_major" 1|0;
  *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays, rt_occluded and rt_radiance),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
- *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does);
+ *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does),
+ *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather and rt_gather_device, 1 KB of partials each);
  *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),
  *   "denoise_lds" 1|0 (1: the filter passes with step 1 and 2 stage tile + halo in LDS, 0: direct loads).
  * RT_E_INVALID for an unknown key or a value out of range. */

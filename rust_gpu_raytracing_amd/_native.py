@@ -93,6 +93,11 @@ class rt_radiance_ray(ctypes.Structure):
                 ("direction", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
 
 
+class rt_gather_point(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_float * 3), ("stream", ctypes.c_uint32),
+                ("normal", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
+
+
 class rt_hit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
                 ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
@@ -116,6 +121,7 @@ assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
 assert ctypes.sizeof(rt_radiance_ray) == 32
+assert ctypes.sizeof(rt_gather_point) == 32 and rt_gather_point.stream.offset == 12 and rt_gather_point.normal.offset == 16
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -157,6 +163,8 @@ SIGNATURES = {
     "rt_occluded_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_radiance": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_radiance_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
+    "rt_gather": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_gather_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_denoise_default_params":(ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
     "rt_compute_features": (ctypes.c_int, [_P]),
     "rt_read_features": (ctypes.c_int, [_P, _P, _P]),

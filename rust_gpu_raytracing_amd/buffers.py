@@ -117,6 +117,9 @@ OCCLUSION_RAY = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", 
 # rt_radiance_ray -- radiance queries (rt_radiance): a QUERY_RAY with the RNG stream in the place of
 # _pad0; the result is four float32 per ray
 RADIANCE_RAY = np.dtype([("origin", "<f4", 3), ("stream", "<u4"), ("direction", "<f4", 3), ("_pad1", "<f4")])
+# rt_gather_point -- gather queries (rt_gather): the layout of RADIANCE_RAY with a surface point and
+# its normal; the result is four float32 per point
+GATHER_POINT = np.dtype([("position", "<f4", 3), ("stream", "<u4"), ("normal", "<f4", 3), ("_pad1", "<f4")])
 # rt_denoise_params -- the guided a-trous filter (rt_denoise); defaults {4, 1.0, 0.1, 0.05}
 DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigma_albedo", "<f4"),
                            ("sigma_depth", "<f4")])
@@ -127,7 +130,7 @@ TEMPORAL_PARAMS = np.dtype([("world_to_pixel", "<f4", 16), ("max_history", "<u4"
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
-    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
+    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
 ):
     assert _dt.itemsize == _size, (_dt, _size)
 

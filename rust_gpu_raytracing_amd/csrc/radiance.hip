@@ -24,6 +24,39 @@
 //  * Each wave's first chunk is its own, by its index in the launch, as in rt_occlusion_kernel.
 //  * Counted ray segments (the rule of rt_ray_count: one per trace_ray call) are summed per lane,
 //    reduced once per wave at exit and added to the caller's counter with one atomic per wave.
+//
+// Gather queries (rt_gather, rt_gather_device) run on the same kernel body,
+// instantiated with kGather, and on rt_gather_resolve_kernel below. The contract, as in
+// include/rt_abi.h:
+//
+// THE GATHER CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+// written order, with no contraction. For point i with record (x, stream, n):
+//  1. Sample index and origin. For s = 0 .. samples-1, u = first_sample + s (u32, wrapping).
+//     o = x + n * 0.0001f per component: one multiply and one add (the reference's bounce
+//     offset, as restated at oracle/pathtrace_oracle.c:511).
+//  2. Direction. dseed = (stream * u * 326624u) ^ 0x9E3779B9u (u32, wrapping).
+//     gx, gy, gz = normal_distribution(&dseed) three times, in that order
+//     (compute_shader.wgsl:622-628, theta drawn before rho).
+//     dir = normalize(n + (gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and
+//     dot(v, v) = (x*x + y*y) + z*z. n is used as given and is not normalised.
+//  3. Path. L_s is the result rt_radiance defines for the record (o, stream, dir) with
+//     first_sample = u, samples = 1 and the call's bounces: per_pixel with its own seed
+//     stream * u * 326624u, its own jitter, and everything else of a frame.
+//  4. Reduction. P_j (j = 0 .. 63) starts at +0.0f on all four channels. For s ascending,
+//     P_{s mod 64} = P_{s mod 64} + L_s. Then, for off = 32, 16, 8, 4, 2, 1:
+//     P_j = P_j + P_{j+off} for every j < off. radiance[i] = P_0. Lanes that got no sample
+//     take part with +0.0f. (An xor butterfly gives the same bits on finite values, because
+//     f32 addition commutes.)
+// End of the gather contract.
+//
+//  * The work item is a (point, stripe) pair: stripe j of a point runs its samples j, j + 64, ...
+//    back to back on one lane, which is step 4's P_j, and stores it among the point's 64
+//    partials. Points with fewer than 64 samples have only `samples` stripes. Three places of
+//    the body differ from a radiance query: the sample start (steps 1 and 2, then
+//    start_sample_at), the sample stride, and where the sum goes.
+//  * rt_gather_resolve_kernel runs step 4's tree: one wave per point, lane j loads P_j (one
+//    coalesced 1 KB read; +0.0f for a stripe the point does not have), six shuffle levels in the
+//    contract's order, one 16-B store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,6 +78,7 @@ struct RadianceArgs {
     unsigned long long claimed_from;            // first ray handed out by the counter: first_chunk x the launch's waves
     uint32_t first_sample;                      // random_index of a ray's first sample (:154)
     uint32_t samples;                           // samples per ray, >= 1 (ka.bounces >= 1 too: the host answers 0)
+    uint32_t stripes;                           // kGather: stripes per point, min(samples, 64)
 };
 
 namespace {
@@ -75,7 +109,10 @@ __device__ __forceinline__ void claim_chunk(const RadianceArgs& qa, uint32_t wav
 
 }  // namespace
 
-template <int kMode, bool kTris, uint32_t kThreads>
+// kGather: the path kernel of a gather query (the contract above). A "ray" is then a (point,
+// stripe) item: qa.rays holds rt_gather_point records, qa.count the launch's items (points x
+// qa.stripes, below 2^32), and qa.radiance the partials, 64 float4 per point.
+template <int kMode, bool kTris, uint32_t kThreads, bool kGather = false>
 __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka, RadianceArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool kAux = kMode >= 1;
@@ -177,10 +214,23 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
 
     // Sample `sample` of the lane's ray: the record is read again (two 16-B loads that hit the
     // cache) instead of holding origin, direction and stream in 7 registers through every walk.
+    // kGather: `ray` is point * 64 + stripe (the item's slot among the partials) and `sample` the
+    // sample index s; the origin and the direction are steps 1 and 2 of the contract.
     auto begin_sample = [&]() {
-        const float4 r0 = qa.rays[2ull * ray], r1 = qa.rays[2ull * ray + 1ull];
-        start_sample_at(mk(r0.x, r0.y, r0.z), __float_as_uint(r0.w), qa.first_sample + sample,
-                        mk(r1.x, r1.y, r1.z), p);
+        if constexpr (kGather) {
+            const float4 r0 = qa.rays[2ull * (ray >> 6)], r1 = qa.rays[2ull * (ray >> 6) + 1ull];
+            const f3 n = mk(r1.x, r1.y, r1.z);
+            const uint32_t stream = __float_as_uint(r0.w), u = qa.first_sample + sample;
+            uint32_t dseed = (stream * u * 326624u) ^ 0x9E3779B9u;
+            const float gx = normal01(dseed);
+            const float gy = normal01(dseed);
+            const float gz = normal01(dseed);
+            start_sample_at(mk(r0.x, r0.y, r0.z) + n * 0.0001f, stream, u, normalize(n + mk(gx, gy, gz)), p);
+        } else {
+            const float4 r0 = qa.rays[2ull * ray], r1 = qa.rays[2ull * ray + 1ull];
+            start_sample_at(mk(r0.x, r0.y, r0.z), __float_as_uint(r0.w), qa.first_sample + sample,
+                            mk(r1.x, r1.y, r1.z), p);
+        }
         mode = kSetup;
     };
 
@@ -202,8 +252,15 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
                 sum.y = sum.y + p.light.y;
                 sum.z = sum.z + p.light.z;
                 sum.w = sum.w + p.light.w;
-                sample += 1;
-                if (sample < qa.samples) {
+                bool more;
+                if constexpr (kGather) {  // the stripe's next sample, 64 on (no wrap: samples - sample >= 1)
+                    more = qa.samples - sample > 64u;
+                    sample += 64u;
+                } else {
+                    sample += 1;
+                    more = sample < qa.samples;
+                }
+                if (more) {
                     begin_sample();
                 } else {
                     qa.radiance[ray] = sum;
@@ -222,8 +279,14 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
                 const uint32_t rank =
                     __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
                 if (rank < avail) {
-                    ray = next + rank;
-                    sample = 0;
+                    if constexpr (kGather) {
+                        const uint32_t item = (uint32_t)(next + rank), point = item / qa.stripes;
+                        sample = item - point * qa.stripes;
+                        ray = (unsigned long long)point * 64u + sample;
+                    } else {
+                        ray = next + rank;
+                        sample = 0;
+                    }
                     sum = make_float4(0.f, 0.f, 0.f, 0.f);
                     begin_sample();
                 }
@@ -335,47 +398,88 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
     }
 }
 
+// Step 4's tree of a gather query: one wave per point. Lane j holds P_j; after the level `off`
+// the lanes below `off` hold the contract's P_j + P_{j+off} (the lanes above hold sums that nothing
+// reads). Stripes the point does not have (samples < 64) take part with +0.0f.
+constexpr uint32_t kResolveThreads = 256;
+__global__ void __launch_bounds__(kResolveThreads) rt_gather_resolve_kernel(const float4* __restrict__ partials,
+                                                                           float4* __restrict__ radiance,
+                                                                           uint32_t points, uint32_t stripes) {
+    const uint32_t point = blockIdx.x * (kResolveThreads / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (point >= points) return;  // wave-uniform
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < stripes) v = partials[(size_t)point * 64u + lane];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        v.x = v.x + __shfl_down(v.x, off, 64);
+        v.y = v.y + __shfl_down(v.y, off, 64);
+        v.z = v.z + __shfl_down(v.z, off, 64);
+        v.w = v.w + __shfl_down(v.w, off, 64);
+    }
+    if (lane == 0) radiance[point] = v;
+}
+
 // Workgroup size by placement. The global-memory instance has no image to share: small workgroups,
 // as the closest-hit query's. The staged instances share one image among as many waves as their
 // registers allow without spilling: the walks from global memory with the shading state live need
 // about 150 VGPRs (the path kernel's figure), which 16 waves per workgroup (128 each) would spill.
 uint32_t rt_radiance_threads(int mode, bool tris) { return mode == 0 ? 256u : (tris && mode == 1) ? 512u : 1024u; }
 
-// (mode, triangles, threads)
+// (mode, triangles, threads); each also as the gather instance
 #define RT_FOR_EACH_RADIANCE(X) \
     X(0, true, 256) X(1, true, 512) X(2, true, 1024) X(0, false, 256) X(1, false, 1024)
 
-// Resident workgroups per CU of the instance at this dynamic LDS size (0: it does not fit).
-hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
-#define RT_ROCC(M, TR, T)                                                                                   \
-    if (mode == M && tris == TR) {                                                                          \
-        const void* fn = reinterpret_cast<const void*>(&rt_radiance_kernel<M, TR, T>);                     \
-        if (lds_bytes > 64u * 1024u) {                                                                      \
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-            if (e != hipSuccess) return e;                                                                  \
-        }                                                                                                   \
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, rt_radiance_kernel<M, TR, T>, T, \
-                                                            lds_bytes);                                    \
+template <class K>
+static hipError_t radiance_occupancy_of(K kernel, uint32_t threads, size_t lds_bytes, int* blocks_per_cu) {
+    if (lds_bytes > 64u * 1024u) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
     }
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kernel, threads, lds_bytes);
+}
+
+// Resident workgroups per CU of the instance at this dynamic LDS size (0: it does not fit).
+hipError_t rt_radiance_occupancy(int mode, bool tris, bool gather, size_t lds_bytes, int* blocks_per_cu) {
+#define RT_ROCC(M, TR, T)                                                                                  \
+    if (mode == M && tris == TR)                                                                           \
+        return gather ? radiance_occupancy_of(&rt_radiance_kernel<M, TR, T, true>, T, lds_bytes, blocks_per_cu) \
+                      : radiance_occupancy_of(&rt_radiance_kernel<M, TR, T, false>, T, lds_bytes, blocks_per_cu);
     RT_FOR_EACH_RADIANCE(RT_ROCC)
 #undef RT_ROCC
     return hipErrorInvalidValue;
 }
 
+// `stripes` 0: a radiance query of `count` rays. Otherwise the path kernel of a gather query:
+// `rays` holds rt_gather_point records, `count` is the launch's items (points x stripes) and
+// `radiance` receives the partials, 64 float4 per point.
 hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
                               const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
                               unsigned long long* segments, uint32_t wave_chunk, uint32_t first_chunk,
-                              uint32_t first_sample, uint32_t samples, hipStream_t stream) {
+                              uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream) {
     if (blocks == 0 || count == 0) return hipSuccess;
     const unsigned long long waves = (unsigned long long)blocks * (rt_radiance_threads(mode, tris) / 64u);
     const RadianceArgs qa{static_cast<const float4*>(rays), static_cast<float4*>(radiance), count, counter, segments,
-                          wave_chunk, first_chunk, waves * first_chunk, first_sample, samples};
-#define RT_RLAUNCH(M, TR, T)                                                                                 \
-    if (mode == M && tris == TR) {                                                                           \
-        hipLaunchKernelGGL((rt_radiance_kernel<M, TR, T>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
-        return hipGetLastError();                                                                            \
+                          wave_chunk, first_chunk, waves * first_chunk, first_sample, samples, stripes};
+#define RT_RLAUNCH(M, TR, T)                                                                                  \
+    if (mode == M && tris == TR) {                                                                            \
+        if (stripes)                                                                                          \
+            hipLaunchKernelGGL((rt_radiance_kernel<M, TR, T, true>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
+        else                                                                                                  \
+            hipLaunchKernelGGL((rt_radiance_kernel<M, TR, T, false>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
+        return hipGetLastError();                                                                             \
     }
     RT_FOR_EACH_RADIANCE(RT_RLAUNCH)
 #undef RT_RLAUNCH
     return hipErrorInvalidValue;
+}
+
+// Step 4's tree over the partials of `points` points (stream-ordered after the path kernel).
+hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
+                                    hipStream_t stream) {
+    if (points == 0) return hipSuccess;
+    const uint32_t per_block = kResolveThreads / 64u;
+    hipLaunchKernelGGL(rt_gather_resolve_kernel, dim3((points + per_block - 1u) / per_block), dim3(kResolveThreads), 0,
+                       stream, static_cast<const float4*>(partials), static_cast<float4*>(radiance), points, stripes);
+    return hipGetLastError();
 }

@@ -64,11 +64,13 @@ hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
                                uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream);
 uint32_t rt_radiance_threads(int mode, bool tris);
-hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_radiance_occupancy(int mode, bool tris, bool gather, size_t lds_bytes, int* blocks_per_cu);
 hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
                               const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
                               unsigned long long* segments, uint32_t wave_chunk, uint32_t first_chunk,
-                              uint32_t first_sample, uint32_t samples, hipStream_t stream);
+                              uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
+hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
+                                    hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
@@ -110,6 +112,9 @@ static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ra
 static_assert(sizeof(rt_radiance_ray) == sizeof(rt_query_ray), "rt_radiance_ray is an rt_query_ray with the stream for _pad0");
 static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ray, direction) == 16,
               "rt_radiance_ray: {origin, stream}, {direction, pad} as two 16-B loads");
+static_assert(sizeof(rt_gather_point) == sizeof(rt_radiance_ray), "rt_gather_point has the layout of rt_radiance_ray");
+static_assert(offsetof(rt_gather_point, stream) == 12 && offsetof(rt_gather_point, normal) == 16,
+              "rt_gather_point: {position, stream}, {normal, pad} as two 16-B loads");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
 static_assert(sizeof(rt_sub_object_info) == sizeof(RtSubObject), "sub-object record");
@@ -181,6 +186,10 @@ constexpr uint32_t kMaxQueryChunk = 1u << 24;
 // A query of fewer rays than this launches the mode-0 instance (the scene read from global
 // memory) instead of staging the LDS image in every workgroup: measured crossover, DESIGN.md §5.4b.
 constexpr uint64_t kQueryStageMinRays = 262144;
+// Gather queries (radiance.hip) run in launches of at most this many points, 1 KB of partials
+// each (16 MiB of context-owned scratch); tuning "gather_chunk".
+constexpr uint32_t kDefaultGatherChunk = 16384;
+constexpr uint32_t kMaxGatherChunk = 1u << 20;
 // Feature buffers (denoise.hip): the frame's camera rays are traced in bands of this many pixels,
 // so the scratch of a band -- its rays and records, 96 B per pixel: 48 MiB -- does not grow with
 // the frame (3840x2160 would take 800 MB at once); tuning "feature_band".
@@ -420,6 +429,9 @@ struct rt_ctx {
     void* query_pinned = nullptr;               // the same on the host, pinned
     size_t query_pinned_rays = 0;
     unsigned long long* d_radiance_segs = nullptr;  // rt_radiance: the batch's counted segments
+    uint32_t gather_chunk = kDefaultGatherChunk;    // tuning "gather_chunk": points per gather launch
+    void* d_gather_partials = nullptr;              // rt_gather: 64 float4 per point of a launch
+    size_t gather_partials_bytes = 0;
     int q_occ_mode = -1;                        // occupancy of the last query instance
     int q_occ_kind = 0;                         // (which kernel's: QueryKind)
     bool q_occ_tris = false;
@@ -920,7 +932,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
                     ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2]};
@@ -1833,11 +1845,12 @@ static int query_enter(rt_ctx* ctx) {
 // The scene view of a query of `count` rays: the frame launches' carve, with the placement capped
 // by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
 // `kind`: the kernel the view is for -- rt_query_kernel, rt_occlusion_kernel (occlusion.hip) or
-// rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples.
-enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2 };
+// rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
+// its gather instance (points x samples).
+enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2, kQueryGather = 3 };
 
 static uint32_t query_threads(int kind, int mode, bool tris) {
-    return kind == kQueryRadiance ? rt_radiance_threads(mode, tris)
+    return kind >= kQueryRadiance ? rt_radiance_threads(mode, tris)
                                   : kind == kQueryAnyHit ? rt_occlusion_threads(mode) : rt_query_threads(mode);
 }
 
@@ -1863,7 +1876,8 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, Sc
         if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_kind != kind ||
             ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != *lds_bytes) {
             int n = 0;
-            const hipError_t e = kind == kQueryRadiance ? rt_radiance_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
+            const hipError_t e = kind >= kQueryRadiance
+                                     ? rt_radiance_occupancy(sl.mode, sl.tris, kind == kQueryGather, *lds_bytes, &n)
                                  : kind == kQueryAnyHit ? rt_occlusion_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
                                                         : rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
             if (e != hipSuccess) (void)hipGetLastError();
@@ -2362,7 +2376,7 @@ static int run_radiance(rt_ctx* ctx, const void* rays, void* radiance, uint64_t 
     RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
     const hipError_t e = rt_launch_radiance(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, radiance, count,
                                             ctx->d_query_next, segments, rest_chunk, first_chunk, first_sample,
-                                            samples, ctx->stream);
+                                            samples, 0u, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel launch", e);
     return RT_OK;
 }
@@ -2421,6 +2435,130 @@ int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint6
         std::memcpy(h_rays, rays + done, n * sizeof(rt_radiance_ray));
         RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_radiance_ray), hipMemcpyHostToDevice, ctx->stream));
         if ((rc = run_radiance(ctx, d_rays, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_rad, d_rad, n * 16u, hipMemcpyDeviceToHost, ctx->stream));
+        done += n;
+        if (done == count)
+            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(radiance + 4u * (done - n), h_rad, n * 16u);
+    }
+    if (segments) *segments = *h_segs;
+    return RT_OK;
+}
+
+// ---- gather queries (radiance.hip, kGather) -----------------------------------------------------
+//
+// Per point, the tree-reduced light of `samples` paths through the diffuse lobe (the contract in
+// include/rt_abi.h). The path kernel is the radiance kernel's gather instance over (point, stripe)
+// items; rt_gather_resolve_kernel reduces each point's partials.
+
+// Gathers at `count` points at device pointer `points` into `radiance`, stream-ordered on the
+// primary stream, in launches of at most "gather_chunk" points; the counted segments are added to
+// the device counter `segments` (null: not counted).
+static int run_gather(rt_ctx* ctx, const void* points, void* radiance, uint64_t count, uint32_t bounces,
+                      uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
+    if (count == 0) return RT_OK;
+    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
+        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
+        return RT_OK;
+    }
+    KernelArgs ka{};
+    SceneLaunch sl;
+    size_t lds_bytes = 0;
+    int per_cu = 0;
+    // the placement threshold of the other queries, on the walks the call runs at least
+    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
+    int rc = query_scene(ctx, ka, walks, kQueryGather, sl, &lds_bytes, &per_cu);
+    if (rc) return rc;
+    ka.bounces = bounces;
+    ka.drain_threshold = ctx->drain_threshold;
+    ka.drain_min_steps = ctx->drain_min_steps;
+    const uint32_t stripes = std::min<uint32_t>(samples, 64u);
+    const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
+    if ((rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u))) return rc;
+    const uint32_t waves_per_block = rt_radiance_threads(sl.mode, sl.tris) / 64u;
+    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
+    for (uint64_t done = 0; done < count;) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
+        // the launch is sized by its items, (point, stripe) pairs: at most 2^20 x 64
+        const uint64_t items = (uint64_t)n * stripes;
+        const uint64_t wanted = (items + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
+        // run_radiance's schedule, over items
+        const uint64_t waves = (uint64_t)blocks * waves_per_block;
+        const uint32_t first_chunk = (uint32_t)std::min<uint64_t>(
+            kRadianceFirstChunkMax, std::max<uint64_t>(64u, (items / waves / 2u) & ~63ull));
+        const uint64_t rest = items > waves * first_chunk ? items - waves * first_chunk : 0;
+        const uint32_t rest_chunk = (uint32_t)std::min<uint64_t>(
+            kRadianceChunkMax, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
+        RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+        hipError_t e = rt_launch_radiance(ka, sl.mode, sl.tris, lds_bytes, blocks,
+                                          static_cast<const unsigned char*>(points) + done * sizeof(rt_gather_point),
+                                          ctx->d_gather_partials, items, ctx->d_query_next, segments, rest_chunk,
+                                          first_chunk, first_sample, samples, stripes, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel (gather) launch", e);
+        e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(radiance) + done * 16u, n,
+                                     stripes, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, "rt_gather_resolve_kernel launch", e);
+        done += n;
+    }
+    return RT_OK;
+}
+
+int rt_gather_device(rt_ctx* ctx, const void* points_device, void* radiance_device, uint64_t count, uint32_t bounces,
+                     uint32_t first_sample, uint32_t samples, void* segments_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_gather_device: samples is 0");
+    if (count == 0) return RT_OK;
+    if (!points_device || !radiance_device)
+        return fail(ctx, RT_E_INVALID, "rt_gather_device: points or radiance is NULL");
+    for (const void* ptr : {points_device, (const void*)radiance_device, (const void*)segments_device}) {
+        if (!ptr) continue;  // (segments may be NULL)
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID,
+                        "rt_gather_device: points, radiance and segments must be device memory of the context's device");
+        }
+    }
+    if (((uintptr_t)points_device | (uintptr_t)radiance_device) & 15u)
+        return fail(ctx, RT_E_INVALID, "rt_gather_device: points and radiance must be 16-byte aligned");
+    if ((uintptr_t)segments_device & 7u)
+        return fail(ctx, RT_E_INVALID, "rt_gather_device: segments must be 8-byte aligned");
+    const int rc = query_enter(ctx);
+    if (rc) return rc;
+    return run_gather(ctx, points_device, radiance_device, count, bounces, first_sample, samples,
+                      static_cast<unsigned long long*>(segments_device));
+}
+
+int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance, uint64_t count, uint32_t bounces,
+              uint32_t first_sample, uint32_t samples, uint64_t* segments) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_gather: samples is 0");
+    if (count == 0) {
+        if (segments) *segments = 0;
+        return RT_OK;
+    }
+    if (!points || !radiance) return fail(ctx, RT_E_INVALID, "rt_gather: points or radiance is NULL");
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    if (!ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    // rt_radiance's staging: the points where its rays go, the results where its sums go
+    unsigned char* d_pts = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_rad = d_pts + ctx->query_buf_rays * sizeof(rt_gather_point);
+    unsigned char* h_pts = static_cast<unsigned char*>(ctx->query_pinned);
+    unsigned char* h_rad = h_pts + ctx->query_pinned_rays * sizeof(rt_gather_point);
+    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_rad + chunk * 16u);
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_pts, points + done, n * sizeof(rt_gather_point));
+        RT_HIP(ctx, hipMemcpyAsync(d_pts, h_pts, n * sizeof(rt_gather_point), hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run_gather(ctx, d_pts, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs))) return rc;
         RT_HIP(ctx, hipMemcpyAsync(h_rad, d_rad, n * 16u, hipMemcpyDeviceToHost, ctx->stream));
         done += n;
         if (done == count)
@@ -2722,6 +2860,8 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         rc = flag(ctx->unit_tile_major);
     } else if (k == "query_chunk") {
         if ((rc = range(1, (int32_t)kMaxQueryChunk)) == RT_OK) ctx->query_chunk = (uint32_t)v;
+    } else if (k == "gather_chunk") {
+        if ((rc = range(1, (int32_t)kMaxGatherChunk)) == RT_OK) ctx->gather_chunk = (uint32_t)v;
     } else if (k == "query_lds_mode") {
         if ((rc = range(-1, 2)) == RT_OK) ctx->query_lds_mode = v;
     } else if (k == "feature_band") {

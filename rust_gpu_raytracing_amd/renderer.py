@@ -458,6 +458,70 @@ class Renderer:
         cur.wait_stream(mine)
         return (out, int(segments.item())) if return_segments else out
 
+    # ------------------------------------------------------------------ gather queries
+    def gather(self, points, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,
+               samples: int = 64, return_segments: bool = False):
+        """The light each surface point gathers (rt_gather): per point, the sum over ``samples``
+        paths that leave the point through the renderer's diffuse lobe -- what a roughness-1,
+        non-specular, non-glass surface there would gather in the reference's per_pixel. The
+        directions are drawn on the device; the sum is the contract's stripe-and-tree reduction
+        (include/rt_abi.h), bit-exact whatever the schedule. Divide by ``samples`` for the mean;
+        nothing is clamped. Against the scene as it is now, without touching anything a render
+        reads.
+
+        ``points``: an (n, 6) float32 array (position, normal; the normal is used as given), with
+        ``streams`` an (n,) uint32 array of RNG streams (default: 1 + the point's position in
+        the batch: stream 0 draws the same sample every time), or a ``buffers.GATHER_POINT``
+        array. Returns an (n, 4) float32 array, and with ``return_segments`` the call's counted
+        ray segments. A CUDA torch tensor of shape (n, 8) float32 (rt_gather_point records: the
+        stream's bits in column 3) goes through rt_gather_device instead -- no host round trip,
+        stream-ordered on the context's stream -- and returns a CUDA (n, 4) float32 tensor."""
+        if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+            if streams is not None:
+                raise ValueError("device points carry their stream in column 3")
+            return self._gather_device(points, bounces, first_sample, samples, return_segments)
+        points = np.asarray(points)
+        if points.dtype == B.GATHER_POINT:
+            if streams is not None:
+                raise ValueError("GATHER_POINT records carry their own stream")
+        else:
+            r = np.ascontiguousarray(points, np.float32)
+            if r.ndim != 2 or r.shape[1] != 6:
+                raise ValueError("points must be (n, 6) float32 or a GATHER_POINT array")
+            points = np.zeros(r.shape[0], B.GATHER_POINT)
+            points["position"] = r[:, :3]
+            points["normal"] = r[:, 3:]
+            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
+            if s.shape != (r.shape[0],):
+                raise ValueError("streams must be an (n,) array")
+            points["stream"] = s
+        points = np.ascontiguousarray(points.reshape(-1))
+        out = np.zeros((points.shape[0], 4), np.float32)
+        segments = ctypes.c_uint64(0)
+        self._call("rt_gather", N.ptr(points), N.ptr(out), points.shape[0], int(bounces), int(first_sample),
+                   int(samples), ctypes.byref(segments))
+        return (out, segments.value) if return_segments else out
+
+    def _gather_device(self, points, bounces, first_sample, samples, return_segments):
+        import torch
+
+        if not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
+            raise ValueError("device points must be a CUDA float32 tensor of shape (n, 8)")
+        if points.device.index != self.device:
+            raise ValueError("device points must live on the renderer's device")
+        points = points.contiguous()
+        out = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+        segments = torch.zeros(1, dtype=torch.int64, device=points.device) if return_segments else None
+        # the stream handshake of _trace_rays_device
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=points.device)
+        cur = torch.cuda.current_stream(points.device)
+        mine.wait_stream(cur)
+        self._call("rt_gather_device", ctypes.c_void_p(points.data_ptr() if points.shape[0] else None),
+                   ctypes.c_void_p(out.data_ptr() if points.shape[0] else None), points.shape[0], int(bounces),
+                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
+        cur.wait_stream(mine)
+        return (out, int(segments.item())) if return_segments else out
+
     # ------------------------------------------------------------------ feature buffers & denoiser
     def compute_features(self) -> None:
         """rt_compute_features: the first-hit feature planes, recomputed only after a camera or

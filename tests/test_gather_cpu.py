@@ -1,0 +1,236 @@
+"""Gather queries without a GPU: the ABI surface (rt_gather_point, the two entry points), the three
+copies of the contract, the NumPy restatement (tests/gather_ref.py) pinned to the oracle's own
+per_pixel, and the contract's reduction against a plain ascending sum.
+
+No kernel launches here; tests/test_gpu_gather.py compares the kernels with the restatement.
+"""
+import ctypes
+import dataclasses
+import functools
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from rust_gpu_raytracing_amd import _native as N
+from rust_gpu_raytracing_amd import buffers as B
+from tests import gather_ref as G
+from tests.golden.fixtures import CASES, load, scene_from_inputs
+
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = ROOT / "include" / "rt_abi.h"
+KERNELS = ROOT / "rust_gpu_raytracing_amd" / "csrc" / "radiance.hip"
+FUNCTIONS = ("rt_gather", "rt_gather_device")
+POINT_FIELDS = ("position", "stream", "normal", "_pad1")
+GOLDEN = {"c1": "c1_64x48_b4", "c2": "c2_64x36_b8", "c3": "c3_64x36_b8"}
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# ---------------------------------------------------------------------------- ABI
+def test_functions_declared_exported_and_bound(native_lib):
+    declared = set(re.findall(r"^RT_API\s+[\w\s\*]+?\b(rt_\w+)\s*\(", HEADER.read_text(), re.M))
+    out = subprocess.run(["nm", "-D", "--defined-only", str(N.LIB_PATH)], capture_output=True, text=True,
+                         check=True).stdout
+    exported = set(re.findall(r"\bT (rt_\w+)", out))
+    for name in FUNCTIONS:
+        assert name in declared
+        assert name in exported
+        assert name in N.SIGNATURES
+        assert hasattr(native_lib, name)
+    assert N.SIGNATURES["rt_gather"] == N.SIGNATURES["rt_radiance"]
+    assert N.SIGNATURES["rt_gather_device"] == N.SIGNATURES["rt_radiance_device"]
+    assert native_lib.rt_abi_version() == 12
+    assert "12, additive: gather queries" in HEADER.read_text()
+
+
+def test_point_layout_against_compiled_header(tmp_path):
+    """sizeof and every field offset of rt_gather_point from a C program compiled against the
+    real header equal the ctypes structure's and the numpy dtype's, and rt_radiance_ray's: 32
+    bytes, offsets 0, 12, 16, 28."""
+    args = ["sizeof(rt_gather_point)"] + [f"offsetof(rt_gather_point, {f})" for f in POINT_FIELDS]
+    args += ["sizeof(rt_radiance_ray)", "offsetof(rt_radiance_ray, stream)", "offsetof(rt_radiance_ray, direction)"]
+    fmt = " ".join(["%zu"] * len(args))
+    src = tmp_path / "off.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rt_abi.h"\n'
+                   f'int main(void){{printf("{fmt}\\n", {", ".join(args)}); return 0;}}\n')
+    exe = tmp_path / "off"
+    subprocess.run(["gcc", "-std=c11", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)], check=True)
+    got = list(map(int, subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()))
+    assert got == [32, 0, 12, 16, 28, 32, 12, 16]
+    assert ctypes.sizeof(N.rt_gather_point) == B.GATHER_POINT.itemsize == 32
+    assert [getattr(N.rt_gather_point, f).offset for f in POINT_FIELDS] == got[1:5]
+    assert [B.GATHER_POINT.fields[f][1] for f in POINT_FIELDS] == got[1:5]
+    assert tuple(f for f, _ in N.rt_gather_point._fields_) == B.GATHER_POINT.names == POINT_FIELDS
+    assert B.GATHER_POINT.fields["stream"][0] == np.dtype("<u4")
+
+
+def test_null_context_fails_cleanly(native_lib):
+    pts = np.zeros(2, B.GATHER_POINT)
+    out = np.full((2, 4), 3.5, np.float32)
+    seg = ctypes.c_uint64(9)
+    assert native_lib.rt_gather(None, N.ptr(pts), N.ptr(out), 2, 4, 1, 8, ctypes.byref(seg)) == N.RT_E_INVALID
+    assert native_lib.rt_gather_device(None, None, None, 2, 4, 1, 8, None) == N.RT_E_INVALID
+    assert (out == 3.5).all() and seg.value == 9
+
+
+def test_gather_chunk_is_a_tuning_key():
+    src = (ROOT / "rust_gpu_raytracing_amd" / "csrc" / "rt_abi.cpp").read_text()
+    body = src[src.index("int rt_set_tuning("):]
+    assert 'k == "gather_chunk"' in body[:body.index("\n}\n")]
+    assert re.search(r"kDefaultGatherChunk = 16384;", src)
+    assert '"gather_chunk" 16384' in HEADER.read_text()
+
+
+def _contract(path, lead):
+    """The gather contract of ``path`` with the comment leader ``lead`` stripped."""
+    lines = path.read_text().splitlines()
+    first = next(i for i, l in enumerate(lines) if l.startswith(lead + " THE GATHER CONTRACT."))
+    last = next(i for i, l in enumerate(lines) if l.startswith(lead + " End of the gather contract."))
+    assert all(l.startswith(lead) for l in lines[first:last + 1])
+    return [l[len(lead):].rstrip() for l in lines[first:last + 1]]
+
+
+def test_contract_text_is_in_header_kernel_source_and_restatement():
+    """The contract in include/rt_abi.h equals the header comment of radiance.hip and the docstring
+    of tests/gather_ref.py line for line, and the lines the restatement is written from are there."""
+    in_header, in_kernels = _contract(HEADER, " *"), _contract(KERNELS, "//")
+    in_ref = _contract(Path(G.__file__), "")
+    assert in_header == in_kernels == in_ref
+    text = "\n".join(in_header)
+    for line in ["u = first_sample + s (u32, wrapping).",
+                 "o = x + n * 0.0001f per component: one multiply and one add",
+                 "dseed = (stream * u * 326624u) ^ 0x9E3779B9u (u32, wrapping).",
+                 "gx, gy, gz = normal_distribution(&dseed) three times, in that order",
+                 "dir = normalize(n + (gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and",
+                 "dot(v, v) = (x*x + y*y) + z*z. n is used as given and is not normalised.",
+                 "first_sample = u, samples = 1 and the call's bounces",
+                 "P_{s mod 64} = P_{s mod 64} + L_s. Then, for off = 32, 16, 8, 4, 2, 1:",
+                 "P_j = P_j + P_{j+off} for every j < off. radiance[i] = P_0."]:
+        assert line in text, line
+
+
+# ---------------------------------------------------------------------------- the restatement
+@functools.lru_cache(maxsize=None)
+def golden_scene(key):
+    g = load(GOLDEN[key])
+    return g, CASES[GOLDEN[key]], scene_from_inputs(g)
+
+
+@functools.lru_cache(maxsize=None)
+def points_of(key, count=24):
+    from oracle import oracle as O
+
+    O.build()
+    g, _, scene = golden_scene(key)
+    pts = G.first_hit_points(O, scene, g["camera_rays"], g["camera_origin"], count)
+    pts.setflags(write=False)
+    return pts
+
+
+def test_tree_and_sequential_on_known_values():
+    """The reduction on values whose order of addition shows: 2^24 first and sixty-four ones."""
+    lights = np.zeros((1, 65, 4), np.float32)
+    lights[0, 0] = 2.0 ** 24
+    lights[0, 1:] = 1.0
+    # sequentially every 1 is absorbed. The stripes give P_0 = 2^24 + 1 -> 2^24 (s = 0 and 64) and
+    # 1 in the other 63; level 32 loses P_32's 1 to P_0 and pairs the rest to 2s, and the levels
+    # after it add 2, 4, 8, 16 and 32 to P_0 exactly
+    assert (G.sequential(lights) == 2.0 ** 24).all()
+    assert (G.tree(lights) == 2.0 ** 24 + 62).all()
+    one = np.arange(12, dtype=np.float32).reshape(1, 3, 4)
+    assert np.array_equal(G.tree(one), one.sum(axis=1))
+    assert np.array_equal(bits(G.tree(np.zeros((2, 5, 4), np.float32))), np.zeros((2, 4), np.uint32))
+
+
+def test_origin_and_direction_arithmetic(oracle_lib):
+    """Steps 1 and 2 on one point, written out operation by operation."""
+    x = np.array([0.3, -1.7, 2.9], np.float32)
+    n = np.array([0.6, 0.0, -1.6], np.float32)  # not unit length: used as given
+    o = G.origin(x, n)
+    for k in range(3):
+        assert o[k] == np.float32(x[k] + np.float32(n[k] * np.float32(0.0001)))
+    stream, u = 5, 77
+    seed = ctypes.c_uint32(((stream * u * 326624) & 0xFFFFFFFF) ^ 0x9E3779B9)
+    g = [G.normal_distribution(seed) for _ in range(3)]
+    v = [np.float32(n[k] + g[k]) for k in range(3)]
+    inv = np.float32(1.0) / np.sqrt(np.float32(np.float32(v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]))
+    d = G.direction(n, stream, u)
+    assert [d[k] for k in range(3)] == [np.float32(v[k] * inv) for k in range(3)]
+    assert abs(float(np.linalg.norm(d.astype(np.float64))) - 1.0) < 1e-6
+    # another sample index, another direction; the same index, the same one
+    assert G.direction(n, stream, u + 1).tobytes() != d.tobytes()
+    assert G.direction(n, stream, u).tobytes() == d.tobytes()
+    # stream 0: both seeds are constant
+    assert G.direction(n, 0, 1).tobytes() == G.direction(n, 0, 2).tobytes()
+
+
+@pytest.mark.parametrize("key", ["c1", "c3"])
+def test_lobe_is_pinned_to_the_oracles_per_pixel(oracle_lib, key):
+    """On a scene whose materials are all roughness 1, specular 0, glass 0, the direction of the
+    second segment that the oracle's per_pixel traces (its trace log) equals, bit for bit, the
+    reference's scatter of the restatement's normalize(n + g), drawn from the seed's state after the
+    three jitter draws: n is the normal of the first hit (the oracle's trace_ray on the logged
+    first segment)."""
+    O = oracle_lib
+    g, case, scene = golden_scene(key)
+    materials = np.ascontiguousarray(scene.materials.copy())
+    materials["roughness"], materials["specular"], materials["glass"] = 1.0, 0.0, 0.0
+    matte = dataclasses.replace(scene, materials=materials)
+    matte.flatten = scene.flatten
+    o = O.Oracle(matte, camera_rays=g["camera_rays"].astype(B.RAY))
+    p = matte.params(accumulate=1, compute_per_frame=1, accumulation_index=3)
+    pixels = np.linspace(1, o.width * o.height - 1, 193).astype(np.uint32)
+    log = np.zeros((2, 6), np.float32)
+    checked = 0
+    for pix in pixels:
+        O.lib().oracle_set_trace_log(log.ctypes.data, 2)
+        try:
+            o.render_pixels(p, 2, [int(pix)], threads=1)
+            got = int(O.lib().oracle_trace_log_count())
+        finally:
+            O.lib().oracle_set_trace_log(None, 0)
+        if got < 2:
+            continue  # the first segment escaped
+        h = o.trace(p, log[0, :3], log[0, 3:])
+        n = np.array([h.nx, h.ny, h.nz], np.float32)
+        seed = ctypes.c_uint32(G.seed_of(int(pix), 3))
+        for _ in range(3):  # the jitter's draws
+            O.lib().oracle_random(ctypes.byref(seed))
+        diffuse = G.lobe(n, seed)
+        # per_pixel's scatter, specular + (diffuse - specular) * roughness at roughness 1: the lerp
+        # rounds twice, so it is `diffuse` only to within those roundings, and the comparison runs
+        # the lerp's own operations (oracle/pathtrace_oracle.c:471, :507) on the restatement's diffuse
+        d = log[0, 3:]
+        specular = d - n * (np.float32(2.0) * np.float32(np.float32(n[0] * d[0] + n[1] * d[1]) + n[2] * d[2]))
+        want = specular + (diffuse - specular) * np.float32(1.0)
+        assert np.array_equal(bits(log[1, 3:]), bits(want)), (pix, log[1, 3:], want)
+        assert np.allclose(want, diffuse, rtol=0, atol=1e-6)
+        # and the second segment starts at the bounce offset of step 1
+        pos = np.array([h.px, h.py, h.pz], np.float32)
+        assert np.array_equal(bits(log[1, :3]), bits(G.origin(pos, n)))
+        checked += 1
+    assert checked >= 30, checked  # (about a third of c1's camera rays hit a sphere)
+
+
+# ---------------------------------------------------------------------------- tree against sum
+@pytest.mark.parametrize("key,samples", [("c1", 200), ("c2", 200), ("c3", 200), ("c1", 65)])
+def test_tree_differs_from_the_sequential_sum(oracle_lib, key, samples):
+    """On 24 first-hit points, streams 1..24: the contract's reduction and the plain ascending
+    sum of the same oracle lights differ in bits on at least 75% of the points, and at least 90%
+    of the results are non-zero -- a kernel that summed in sample order would fail the GPU tests."""
+    _, case, scene = golden_scene(key)
+    pts = points_of(key)
+    streams = np.arange(1, 25, dtype=np.uint32)
+    lights, segs = G.oracle_lights(oracle_lib, scene, pts, streams, case["bounces"], 1, samples)
+    tree, seq = G.tree(lights), G.sequential(lights)
+    differ = int((bits(tree) != bits(seq)).any(axis=1).sum())
+    nonzero = int(bits(tree).any(axis=1).sum())
+    print(f"{key} samples {samples}: {differ}/24 differ, {nonzero}/24 non-zero, {int(segs.sum())} segments")
+    assert 4 * differ >= 3 * 24, differ
+    assert 10 * nonzero >= 9 * 24, nonzero
+    assert np.allclose(tree, seq, rtol=1e-4, atol=1e-6)

@@ -1,7 +1,8 @@
 """Throughput of the ray-query kernel (rt_trace_rays_device) and its placement crossover.
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
-                                   [--reps 20] [--sweep] [--out profiles/query_bench.jsonl]
+                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather]
+                                   [--out profiles/query_bench.jsonl]
 
 Rays: the configuration's width x height camera rays (coherent: neighbouring rays are
 neighbouring pixels), and the same rays in a fixed random permutation (incoherent). They live in
@@ -33,6 +34,18 @@ first query equals the first frame's accumulation bit for bit); Mray/s from the 
 device events, and from rt_ray_count over the launch spans. The closest-hit query of the same rays
 is timed next to them. Median, minimum and maximum over --rounds rounds after --settle-ms of
 untimed work.
+--gather: the gather query (rt_gather_device) against the same paths done by hand, in one process
+(DESIGN.md §5.4g). --points points (4,096) are taken from the first hits of the camera rays,
+streams 1..n, at --samples samples (1,024). The yardstick is what a caller without rt_gather does:
+the contract's records generated once on the host (tools/gather_records.c, compiled here against
+the CPU oracle's library) and traced by one rt_radiance_device call with samples = 1 and
+first_sample = 1 (each record's stream is stream * u, which gives the contract's seed): that code
+is the parent's. The records are laid out sample-major (neighbouring records are neighbouring
+points) and point-major (a point's samples are consecutive), each its own series. Each round
+checks that all trace equal segments and that the contract's tree over the by-hand results equals
+the gather bit for bit. Next to them: rt_radiance_device on the points' first records at samples
+= --samples, the shape the gather call replaces (one direction per point, its samples back to
+back on one lane). Device events on the context's stream; median, minimum and maximum over --rounds.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -226,6 +239,148 @@ def radiance_bench(r, args, scene, bounces, dev, emit):
          closest_hit_ratio=round(n / med(hit_ms) / 1e3 / med(frame_rate), 3), build=r._lib.rt_build_hash().decode())
 
 
+def build_gather_records():
+    """tools/gather_records.c as a shared library next to the oracle's (compiled on first use)."""
+    import subprocess
+
+    from oracle import oracle as O
+
+    oracle_so = O.build()
+    src = Path(__file__).resolve().parent / "gather_records.c"
+    out = oracle_so.parent / "libgather_records.so"
+    if not out.exists() or out.stat().st_mtime < max(src.stat().st_mtime, oracle_so.stat().st_mtime):
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-fPIC", "-shared", "-std=c11",
+                        "-Wall", "-o", str(out), str(src), f"-L{oracle_so.parent}", "-l:" + oracle_so.name,
+                        "-Wl,-rpath,$ORIGIN", "-lm"], check=True)
+    lib = ctypes.CDLL(str(out))
+    lib.gather_records.restype = None
+    lib.gather_records.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                   ctypes.c_void_p]
+    return lib
+
+
+def gather_bench(r, args, scene, bounces, dev, emit):
+    """The --gather series (module docstring)."""
+    import statistics
+
+    import torch
+
+    n, samples, first = args.points, args.samples, 1
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+    P = ctypes.c_void_p
+
+    # the points: first hits of the camera rays, spread evenly over the image
+    q = camera_query_rays(scene)
+    q_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    hits_t = torch.empty((q.shape[0], 16), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    r._call("rt_trace_rays_device", P(q_t.data_ptr()), P(hits_t.data_ptr()), q.shape[0])
+    r.synchronize()
+    h = hits_t.cpu().numpy().view(B.HIT).reshape(-1)
+    hit = np.nonzero(h["kind"] != B.HIT_MISS)[0]
+    assert hit.shape[0] >= n, (hit.shape[0], n)
+    pick = hit[np.linspace(0, hit.shape[0] - 1, n).astype(np.int64)]
+    points = np.zeros(n, B.GATHER_POINT)
+    points["position"], points["normal"] = h["position"][pick], h["normal"][pick]
+    points["stream"] = 1 + np.arange(n, dtype=np.uint32)
+    del q_t, hits_t
+
+    # the by-hand records in both orders (streams folded: one call traces them all)
+    helper = build_gather_records()
+    rec_t, host_ms = {}, {}
+    for order, point_major in (("sample_major", 0), ("point_major", 1)):
+        t0 = time.perf_counter()
+        records = np.zeros((samples * n, 8), np.float32)
+        helper.gather_records(points.ctypes.data, n, first, samples, point_major, records.ctypes.data)
+        host_ms[order] = (time.perf_counter() - t0) * 1e3
+        rec_t[order] = torch.from_numpy(records).to(dev)
+    # the shape the call replaces: each point's first direction, the point's own stream
+    long_rec = records.reshape(n, samples, 8)[:, 0].copy()
+    long_rec.view(np.uint32)[:, 3] = points["stream"]
+    long_rec_t = torch.from_numpy(long_rec).to(dev)
+    points_t = torch.from_numpy(points.view(np.float32).reshape(-1, 8)).to(dev)
+    hand_t = torch.empty((samples * n, 4), dtype=torch.float32, device=dev)
+    gather_t = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    long_t = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    seg_t = torch.zeros(4, dtype=torch.int64, device=dev)  # by hand in both orders, gather, the replaced shape
+    torch.cuda.synchronize()
+    seg = [P(seg_t.data_ptr() + 8 * i) for i in range(4)]
+
+    def by_hand(order, counter):
+        r._call("rt_radiance_device", P(rec_t[order].data_ptr()), P(hand_t.data_ptr()), n * samples, bounces, 1, 1,
+                seg[counter])
+
+    def gather():
+        r._call("rt_gather_device", P(points_t.data_ptr()), P(gather_t.data_ptr()), n, bounces, first, samples, seg[2])
+
+    def replaced():
+        r._call("rt_radiance_device", P(long_rec_t.data_ptr()), P(long_t.data_ptr()), n, bounces, first, samples, seg[3])
+
+    def tree(lights):  # step 4 of the contract on (samples, n, 4): torch's f32 add is the IEEE one
+        p = torch.zeros((64, n, 4), dtype=torch.float32, device=dev)
+        for k in range(0, samples, 64):
+            m = min(64, samples - k)
+            p[:m] = p[:m] + lights[k:k + m]
+        off = 32
+        while off:
+            p[:off] = p[:off] + p[off:2 * off]
+            off //= 2
+        return p[0]
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        fn()
+        t1.record(stream)
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    def hand_tree(order):  # the contract's tree over what the by-hand call just wrote
+        r.synchronize()
+        lights = hand_t.view(samples, n, 4) if order == "sample_major" else hand_t.view(n, samples, 4).permute(1, 0, 2)
+        ok = bool(torch.equal(tree(lights).view(torch.int32), gather_t.view(torch.int32)))
+        torch.cuda.synchronize()
+        return ok
+
+    for fn in (lambda: by_hand("sample_major", 0), lambda: by_hand("point_major", 1), gather, replaced):
+        fn()  # warm-up of every shape and placement
+    r.synchronize()
+    ms = {"by_hand_sample_major": [], "by_hand_point_major": [], "gather": [], "replaced": []}
+    segments, same = [], []
+    for _ in range(args.rounds):
+        seg_t.zero_()
+        gather_t.zero_()
+        torch.cuda.synchronize()
+        ms["gather"].append(timed(gather))
+        assert bool(gather_t.view(torch.int32).any())
+        ok = []
+        for counter, order in enumerate(("sample_major", "point_major")):
+            hand_t.zero_()
+            torch.cuda.synchronize()
+            ms["by_hand_" + order].append(timed(lambda: by_hand(order, counter)))
+            ok.append(hand_tree(order))
+        ms["replaced"].append(timed(replaced))
+        r.synchronize()
+        counted = [int(v) for v in seg_t.cpu().numpy()]
+        assert counted[0] == counted[1] == counted[2], counted
+        assert all(ok), "the tree over the by-hand results differs from the gather"
+        segments.append(counted)
+        same.append(all(ok))
+    med = statistics.median
+    ms["by_hand"] = min(ms["by_hand_sample_major"], ms["by_hand_point_major"], key=med)  # the faster order is the yardstick
+    row = {k + "_ms": round(med(v), 3) for k, v in ms.items()}
+    row.update({k + "_ms_min": round(min(v), 3) for k, v in ms.items()})
+    row.update({k + "_ms_max": round(max(v), 3) for k, v in ms.items()})
+    emit(kind="gather", bounces=bounces, points=n, samples=samples, rounds=args.rounds, paths=n * samples,
+         segments_per_path=round(segments[0][2] / (n * samples), 4), segments_equal=True, tree_bit_identical=all(same),
+         gather_over_by_hand=round(med(ms["gather"]) / med(ms["by_hand"]), 4),
+         gather_over_replaced=round(med(ms["gather"]) / med(ms["replaced"]), 4),
+         replaced_segments_per_path=round(segments[0][3] / (n * samples), 4),
+         gather_mray_s=round(segments[0][2] / med(ms["gather"]) / 1e3, 1),
+         by_hand_mray_s=round(segments[0][0] / med(ms["by_hand"]) / 1e3, 1),
+         records_host_ms=round(min(host_ms.values()), 1), records_mb=round(records.nbytes / 2 ** 20, 1), build=r._lib.rt_build_hash().decode(), **row)
+
+
 def main():
     import torch
 
@@ -238,7 +393,10 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
     ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
-    ap.add_argument("--bounces", type=int, default=None, help="--radiance: bounce limit (default: the configuration's)")
+    ap.add_argument("--gather", action="store_true", help="the gather query against the same paths done by hand")
+    ap.add_argument("--points", type=int, default=4096, help="--gather: surface points")
+    ap.add_argument("--samples", type=int, default=1024, help="--gather: samples per point")
+    ap.add_argument("--bounces", type=int, default=None, help="--radiance, --gather: bounce limit (default: the configuration's)")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="--radiance: untimed work before the rounds")
     ap.add_argument("--rounds", type=int, default=7, help="--occluded, --radiance: rounds the series alternate over")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
@@ -269,7 +427,9 @@ def main():
     call = "rt_occluded_device" if args.occluded else "rt_trace_rays_device"
     tuning = {k: int(v) for k, v in (kv.split("=", 1) for kv in args.tune)}
     with Renderer(scene, tuning=tuning) as r:
-        if args.radiance:
+        if args.gather:
+            gather_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
+        elif args.radiance:
             radiance_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
         elif args.occluded and not args.sweep:
             occlusion_bench(r, args, q, dev, emit)
