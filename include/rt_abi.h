@@ -52,7 +52,9 @@ extern "C" {
  * 12, additive: radiance queries (rt_radiance, rt_radiance_device, rt_radiance_ray);
  * 12, additive: temporal denoiser (rt_denoise_temporal, rt_temporal_reset, rt_read_temporal,
  * rt_temporal_default_params, rt_temporal_params);
- * 12, additive: gather queries (rt_gather, rt_gather_device, rt_gather_point). */
+ * 12, additive: gather queries (rt_gather, rt_gather_device, rt_gather_point);
+ * 12, additive: display transform (rt_display, rt_read_display, rt_copy_display_to_device,
+ * rt_display_state, rt_display_reset, rt_display_default_params, rt_display_params). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -843,6 +845,146 @@ RT_API int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* params,
                                const rt_denoise_params* denoise_params /* NULL: defaults */);
 RT_API int rt_temporal_reset(rt_ctx* ctx);
 RT_API int rt_read_temporal(rt_ctx* ctx, float* rgba /* W*H*4 */, float* history /* W*H */);
+
+/* ---- the display transform (ABI 12, additive: display transform) ------------------------
+ *
+ * Radiance to display codes on the device. The frame output, rt_denoise and rt_denoise_temporal all
+ * finish with clamp01 and the truncating pack (the reference's pack_to_u32): with emitters far above
+ * 1 much of a frame lands at 255. rt_display meters the source, adapts an exposure over time, applies
+ * a tone curve and optionally encodes to sRGB, stream-ordered and with no host round trip. The
+ * reference's look stays the default everywhere else.
+ *
+ * THE DISPLAY CONTRACT (tests/display_ref.py restates it from here).
+ *
+ * Everything is f32 unless marked integer. Each written operation is one IEEE operation, in the
+ * written order, with no contraction and correctly rounded division. No exp, log or pow is used.
+ *
+ * S(p) is the source pixel, with four channels: accumulation(p) / D on all four channels (exactly
+ * rt_denoise's c0) for RT_DISPLAY_ACCUMULATION, the f32 result of the last denoise call for
+ * RT_DISPLAY_DENOISED, the caller's plane for RT_DISPLAY_PLANE.
+ *
+ * 1. Metering (only when auto_exposure == 1).
+ *   Per pixel, L = (0.2126f*S.r + 0.7152f*S.g) + 0.0722f*S.b.
+ *   The pixel is metered iff L > 0 && L < +inf. Both tests are false for NaN.
+ *   Its bin is an integer: j = clamp((int)(bits(L) >> 20) - 888, 0, 255).
+ *     This gives 8 bins per octave over [2^-16, 2^16). 888 = (127-16)*8.
+ *     Smaller values go to bin 0, larger ones to bin 255.
+ *   hist[j] += 1.
+ *   The histogram is a set of integer counts, so it is independent of schedule and order.
+ *
+ * 2. Exposure solve (integer until the last line; u64).
+ *   total = sum of hist.
+ *   lo = total*low_permille/1000.
+ *   hi = total - total*high_permille/1000.
+ *   Walking j ascending with a running sum cum, n_j = |[cum, cum+hist[j]) intersected with [lo, hi)|.
+ *   Nn = sum of n_j and Sn = sum of n_j*(2j+1).
+ *   If total == 0: there is no target.
+ *   Otherwise:
+ *     a = (2*Sn + Nn) / (2*Nn). This is the mean bin centre in 1/16 octaves, rounded. It is in 1..511.
+ *     n = 256 - a, q = floor(n / 16), r = n - 16*q.
+ *     E_t = key * ldexpf(T16[r], q).
+ *     E_t = min(max(E_t, min_exposure), max_exposure).
+ *   T16[r] is 2^(r/16) rounded to f32. Its bits are:
+ *     0x3f800000, 0x3f85aac3, 0x3f8b95c2, 0x3f91c3d3, 0x3f9837f0, 0x3f9ef532, 0x3fa5fed7, 0x3fad583f,
+ *     0x3fb504f3, 0x3fbd08a4, 0x3fc5672a, 0x3fce248c, 0x3fd744fd, 0x3fe0ccdf, 0x3feac0c7, 0x3ff5257d.
+ *
+ * 3. Adaptation. E_prev is the state.
+ *   State none, target none: E = min(max(1.0f, min_exposure), max_exposure).
+ *   State none, target E_t: E = E_t.
+ *   State E_prev, target none: E = E_prev.
+ *   State E_prev, target E_t: E = E_prev + (E_t - E_prev)*adaptation.
+ *   The state becomes E.
+ *   With auto_exposure == 0: E = params.exposure. The state and the stored histogram are left untouched.
+ *
+ * 4. Tone curve, per colour channel.
+ *   x = S.c * E.
+ *   x = x > 0 ? x : 0. NaN and -0 give +0.
+ *   x = min(x, 65536.0f).
+ *   LINEAR: y = x.
+ *   REINHARD: iw2 = 1.0f/(white*white), computed on the host in f32; y = (x*(1.0f + x*iw2)) / (1.0f + x).
+ *   ACES: y = (x*(2.51f*x + 0.03f)) / (x*(2.43f*x + 0.59f) + 0.14f).
+ *   Then y = min(y, 1.0f).
+ *   Alpha is clamp01(S.a) with no exposure and no curve (NaN gives 0, as in the frame's clamp). It is
+ *   always packed as the frame packs it.
+ *
+ * 5. Encode.
+ *   NONE: code = (uint32_t)(y*255.0f) & 0xff, which is pack_rgba8.
+ *   SRGB: code is the largest j in 0..255 with srgb_table[j] <= y.
+ *     The table is the 256-entry table of rt_srgb_table.
+ *     It is strictly increasing, so a branch-free 8-step search finds j.
+ *   The packed word is r | g<<8 | b<<16 | a<<24.
+ * End of the display contract.
+ *
+ * Consequences:
+ *  - With auto_exposure = 0, exposure = 1, RT_TONE_LINEAR and RT_ENCODE_NONE the display equals
+ *    rt_read_output of the same frame for RT_DISPLAY_ACCUMULATION, and the packed result of
+ *    rt_read_denoised for RT_DISPLAY_DENOISED.
+ *  - Exposure resolution is 1/16 stop.
+ *  - The SRGB encode is the exact inverse of the texture decode: encode(srgb_table[j]) == j.
+ *
+ * rt_display is an observation point exactly like rt_denoise. For RT_DISPLAY_ACCUMULATION queued
+ * frames launch first; the other sources leave them queued. Everything is stream-ordered on
+ * rt_stream(ctx) and asynchronous; there is no host synchronisation anywhere in it: the adapted
+ * exposure lives in device memory and is consumed there. It changes nothing that a render, a query,
+ * rt_denoise or rt_denoise_temporal observes: the accumulation, the output, k, rt_ray_count, the
+ * timing totals, the tile schedule, the feature planes, the denoised buffers and the temporal history
+ * are untouched. It does not run the denoiser: RT_DISPLAY_DENOISED reads what the last rt_denoise or
+ * rt_denoise_temporal left. Its buffers (one packed u32 plane, 256 live and 256 kept u32 bins and four
+ * words of state) are allocated on first use and freed by rt_destroy. params == NULL:
+ * rt_display_default_params. plane_device: RT_DISPLAY_PLANE's float4 plane of width*height pixels,
+ * row-major, in device memory of the context's device, 16-byte aligned; the caller orders its
+ * producers before rt_stream(ctx).
+ * RT_E_INVALID, with the exposure state and the display plane left as they were: a rank context
+ * (world_size > 1); an unknown source, operator or encode value, or auto_exposure above 1;
+ * RT_DISPLAY_ACCUMULATION with Params.accumulate != 1 or with no frame since the last reset
+ * (rt_denoise's two conditions); RT_DISPLAY_DENOISED before any denoise call; RT_DISPLAY_PLANE with a
+ * pointer that is NULL, not device memory of the context's device or not 16-byte aligned; a non-NULL
+ * pointer with another source; auto_exposure == 0 with exposure not finite or <= 0; auto_exposure == 1
+ * with key, min_exposure or max_exposure not finite or <= 0, min_exposure > max_exposure, adaptation
+ * outside (0, 1] or low_permille + high_permille >= 1000; RT_TONE_REINHARD with white not finite or <= 0.
+ * rt_read_display: synchronous; the packed RGBA8 plane (width*height u32) of the last rt_display; the
+ *   pointer may be NULL. RT_E_INVALID before any rt_display.
+ * rt_copy_display_to_device: rt_copy_denoised_to_device for the display plane, with the same arguments
+ *   and errors; RT_E_INVALID before any rt_display. Asynchronous.
+ * rt_display_state: synchronous; any pointer may be NULL. *exposure: the adapted exposure E (0.0f when
+ *   there is none: before the first auto-exposure call and after rt_display_reset); histogram[256] and
+ *   *metered: the bins and the metered pixel count (total) of the last auto-exposure call, zeros before
+ *   the first.
+ * rt_display_reset: drops the adapted exposure (the next auto-exposure call starts from "state none");
+ *   RT_OK when there is none. */
+#define RT_DISPLAY_ACCUMULATION 0u  /* c = accumulation / D, exactly rt_denoise's c0 */
+#define RT_DISPLAY_DENOISED     1u  /* the f32 result of the last rt_denoise / rt_denoise_temporal */
+#define RT_DISPLAY_PLANE        2u  /* a caller's float4 plane of width*height pixels in device memory */
+#define RT_TONE_LINEAR   0u
+#define RT_TONE_REINHARD 1u         /* extended Reinhard with a white point */
+#define RT_TONE_ACES     2u         /* Narkowicz's rational fit */
+#define RT_ENCODE_NONE 0u           /* the frame's truncating pack (the reference's look) */
+#define RT_ENCODE_SRGB 1u           /* inverse of the texture decode table, by search */
+
+typedef struct rt_display_params {
+    uint32_t source, tone_operator, encode, auto_exposure;
+    float exposure;        /* used as E when auto_exposure == 0 */
+    float key;             /* auto: the luminance the metered average is mapped to */
+    float min_exposure, max_exposure;
+    float adaptation;      /* auto: in (0, 1]; the share of the way to the target taken per call */
+    float white;           /* RT_TONE_REINHARD: the input that maps to 1 */
+    uint32_t low_permille, high_permille; /* auto: darkest / brightest share of metered pixels ignored */
+} rt_display_params;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_display_params) == 48, "rt_display_params is 48 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_display_params) == 48, "rt_display_params is 48 bytes");
+#endif
+
+/* {ACCUMULATION, REINHARD, SRGB, 1,  1.0f, 0.18f, 1/64.f, 64.0f, 1.0f, 4.0f, 100, 50} */
+RT_API int rt_display_default_params(rt_display_params* out);
+RT_API int rt_display(rt_ctx* ctx, const rt_display_params* params /* NULL: defaults */,
+                      const void* plane_device /* RT_DISPLAY_PLANE only, else must be NULL */);
+RT_API int rt_read_display(rt_ctx* ctx, uint32_t* rgba8_out);
+RT_API int rt_copy_display_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row);
+RT_API int rt_display_state(rt_ctx* ctx, float* exposure, uint32_t* histogram /* 256 */, uint64_t* metered);
+RT_API int rt_display_reset(rt_ctx* ctx);
 
 /* Readback (new: the reference only blits output_data to the swapchain,
  * src/renderer.rs:254-283). Synchronous; whole framebuffer, row-major

@@ -115,7 +115,15 @@ class rt_temporal_params(ctypes.Structure):
                 ("sigma_position", ctypes.c_float), ("normal_min", ctypes.c_float), ("_reserved", ctypes.c_uint32)]
 
 
+class rt_display_params(ctypes.Structure):
+    _fields_ = [("source", ctypes.c_uint32), ("tone_operator", ctypes.c_uint32), ("encode", ctypes.c_uint32),
+                ("auto_exposure", ctypes.c_uint32), ("exposure", ctypes.c_float), ("key", ctypes.c_float),
+                ("min_exposure", ctypes.c_float), ("max_exposure", ctypes.c_float), ("adaptation", ctypes.c_float),
+                ("white", ctypes.c_float), ("low_permille", ctypes.c_uint32), ("high_permille", ctypes.c_uint32)]
+
+
 assert ctypes.sizeof(rt_params) == 48
+assert ctypes.sizeof(rt_display_params) == 48
 assert ctypes.sizeof(rt_temporal_params) == 80
 assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
@@ -176,6 +184,12 @@ SIGNATURES = {
     "rt_denoise_temporal": (ctypes.c_int, [_P, ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_denoise_params)]),
     "rt_temporal_reset": (ctypes.c_int, [_P]),
     "rt_read_temporal": (ctypes.c_int, [_P, _P, _P]),
+    "rt_display_default_params": (ctypes.c_int, [ctypes.POINTER(rt_display_params)]),
+    "rt_display": (ctypes.c_int, [_P, ctypes.POINTER(rt_display_params), _P]),
+    "rt_read_display": (ctypes.c_int, [_P, _P]),
+    "rt_copy_display_to_device": (ctypes.c_int, [_P, _P, _U32]),
+    "rt_display_state": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float), _P, ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_display_reset": (ctypes.c_int, [_P]),
     "rt_read_output_pitched": (ctypes.c_int, [_P, _P, _U32]),
     "rt_bytes_per_row": (_U32, [_U32, _U32]),
     "rt_ray_count": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
@@ -255,6 +269,9 @@ RT_PASS_PATH, RT_PASS_PRIMARY, RT_PASS_RESOLVE, RT_PASS_BRUTE, RT_PASS_BRUTE_STR
 RT_GROUP_COPY_TRANSPORT = 1  # rt_create_multi_ex flags
 RT_GATHER_IMAGE = 0
 RT_GATHER_ACCUMULATION = 1
+RT_DISPLAY_ACCUMULATION, RT_DISPLAY_DENOISED, RT_DISPLAY_PLANE = 0, 1, 2  # rt_display_params.source
+RT_TONE_LINEAR, RT_TONE_REINHARD, RT_TONE_ACES = 0, 1, 2                  # rt_display_params.tone_operator
+RT_ENCODE_NONE, RT_ENCODE_SRGB = 0, 1                                     # rt_display_params.encode
 
 _lib = None
 

@@ -126,11 +126,17 @@ DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigm
 # rt_temporal_params -- temporal reprojection (rt_denoise_temporal); defaults {0 matrix, 32, 0.02, 0.9, 0}
 TEMPORAL_PARAMS = np.dtype([("world_to_pixel", "<f4", 16), ("max_history", "<u4"), ("sigma_position", "<f4"),
                             ("normal_min", "<f4"), ("_reserved", "<u4")])
+# rt_display_params -- the display transform (rt_display); defaults
+# {accumulation, Reinhard, sRGB, auto, 1.0, 0.18, 1/64, 64.0, 1.0, 4.0, 100, 50}
+DISPLAY_PARAMS = np.dtype([("source", "<u4"), ("tone_operator", "<u4"), ("encode", "<u4"), ("auto_exposure", "<u4"),
+                           ("exposure", "<f4"), ("key", "<f4"), ("min_exposure", "<f4"), ("max_exposure", "<f4"),
+                           ("adaptation", "<f4"), ("white", "<f4"), ("low_permille", "<u4"), ("high_permille", "<u4")])
 
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
     (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
+    (DISPLAY_PARAMS, 48),
 ):
     assert _dt.itemsize == _size, (_dt, _size)
 

@@ -84,6 +84,13 @@ hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const f
                               float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
                               uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
                               hipStream_t stream);
+hipError_t rt_launch_display_meter(const float4* src, uint64_t n, float div, uint32_t* bins, hipStream_t stream);
+hipError_t rt_launch_display_solve(uint32_t* bins, uint32_t* kept, uint32_t* state, uint32_t low_permille,
+                                   uint32_t high_permille, float key, float min_exposure, float max_exposure,
+                                   float adaptation, bool has_state, hipStream_t stream);
+hipError_t rt_launch_display_tone(const float4* src, uint32_t* dst, uint64_t n, float div, const uint32_t* state,
+                                  float exposure, float iw2, const float* srgb, uint32_t op, uint32_t encode,
+                                  hipStream_t stream);
 hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
                              uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
                              uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
@@ -108,6 +115,7 @@ static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
 static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
 static_assert(sizeof(rt_temporal_params) == 80, "rt_temporal_params is 80 bytes");
+static_assert(sizeof(rt_display_params) == 48, "rt_display_params is 48 bytes");
 static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
 static_assert(sizeof(rt_radiance_ray) == sizeof(rt_query_ray), "rt_radiance_ray is an rt_query_ray with the stream for _pad0");
 static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ray, direction) == 16,
@@ -196,6 +204,9 @@ constexpr uint32_t kMaxGatherChunk = 1u << 20;
 constexpr uint32_t kDefaultFeatureBand = 1u << 19;
 constexpr uint32_t kMaxFeatureBand = 1u << 24;
 constexpr uint32_t kMaxDenoiseIterations = 8;
+// The display transform's metering buffer (display.hip): live bins | kept bins | {E, -, metered lo, hi}.
+constexpr uint32_t kDispBins = 256;
+constexpr uint32_t kDispStateWords = 4;
 
 }  // namespace
 
@@ -464,6 +475,11 @@ struct rt_ctx {
     int t_cur = 0;            // the slot the last rt_denoise_temporal wrote (when valid)
     int t_prev = -1;          // the slot it read; -1: none
     uint64_t accum_gen = 0;   // G
+    // the display transform (rt_display; display.hip), allocated on first use
+    uint32_t* d_disp_out = nullptr;    // the packed display plane
+    uint32_t* d_disp_meter = nullptr;  // kDispBins live bins, kDispBins kept bins, kDispStateWords of state
+    bool disp_valid = false;           // an rt_display has written d_disp_out
+    bool disp_exposure_valid = false;  // the state's exposure word holds an adapted exposure
 
     std::string err;
 };
@@ -933,7 +949,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
                     ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
-                    ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out,
+                    ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out, ctx->d_disp_out, ctx->d_disp_meter,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
                     ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2]};
     for (void* b : bufs)
@@ -2268,6 +2284,147 @@ int rt_read_temporal(rt_ctx* ctx, float* rgba, float* history) {
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (history)
         for (size_t i = 0; i < (size_t)ctx->n_pixels; i++) history[i] = nn[4 * i + 3];
+    return RT_OK;
+}
+
+// ---- the display transform (display.hip) ---------------------------------------------------------
+//
+// Radiance to display codes on the device: meter the source into 256 integer bins, solve and adapt
+// the exposure in one wave, tone-map and encode. Three stream-ordered launches and no host wait:
+// the exposure lives in d_disp_meter and the tone kernel reads it there. Every argument is checked
+// before the first launch, so a failing call leaves the exposure state and the display plane alone.
+int rt_display_default_params(rt_display_params* out) {
+    if (!out) return RT_E_INVALID;
+    *out = rt_display_params{RT_DISPLAY_ACCUMULATION, RT_TONE_REINHARD, RT_ENCODE_SRGB, 1u, 1.0f, 0.18f,
+                             1.0f / 64.0f, 64.0f, 1.0f, 4.0f, 100u, 50u};
+    return RT_OK;
+}
+
+int rt_display(rt_ctx* ctx, const rt_display_params* params, const void* plane_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    rt_display_params dp;
+    (void)rt_display_default_params(&dp);
+    if (params) dp = *params;
+    auto positive = [](float v) { return std::isfinite(v) && v > 0.0f; };
+    if (ctx->world > 1)
+        return fail(ctx, RT_E_INVALID, "rt_display: a rank context (world_size > 1) has no full frame");
+    if (dp.source > RT_DISPLAY_PLANE) return fail(ctx, RT_E_INVALID, "rt_display: unknown source");
+    if (dp.tone_operator > RT_TONE_ACES) return fail(ctx, RT_E_INVALID, "rt_display: unknown tone operator");
+    if (dp.encode > RT_ENCODE_SRGB) return fail(ctx, RT_E_INVALID, "rt_display: unknown encode");
+    if (dp.auto_exposure > 1u) return fail(ctx, RT_E_INVALID, "rt_display: auto_exposure must be 0 or 1");
+    if (dp.source != RT_DISPLAY_PLANE && plane_device)
+        return fail(ctx, RT_E_INVALID, "rt_display: plane_device must be NULL unless the source is RT_DISPLAY_PLANE");
+    if (dp.auto_exposure) {
+        if (!positive(dp.key) || !positive(dp.min_exposure) || !positive(dp.max_exposure))
+            return fail(ctx, RT_E_INVALID, "rt_display: key, min_exposure and max_exposure must be finite and > 0");
+        if (dp.min_exposure > dp.max_exposure)
+            return fail(ctx, RT_E_INVALID, "rt_display: min_exposure > max_exposure");
+        if (!(dp.adaptation > 0.0f && dp.adaptation <= 1.0f))
+            return fail(ctx, RT_E_INVALID, "rt_display: adaptation must be in (0, 1]");
+        if ((uint64_t)dp.low_permille + dp.high_permille >= 1000u)
+            return fail(ctx, RT_E_INVALID, "rt_display: low_permille + high_permille must be < 1000");
+    } else if (!positive(dp.exposure)) {
+        return fail(ctx, RT_E_INVALID, "rt_display: exposure must be finite and > 0");
+    }
+    if (dp.tone_operator == RT_TONE_REINHARD && !positive(dp.white))
+        return fail(ctx, RT_E_INVALID, "rt_display: white must be finite and > 0");
+    const float4* src = nullptr;
+    float div = 1.0f;
+    if (dp.source == RT_DISPLAY_ACCUMULATION) {
+        // an observation point, like rt_denoise: the queued frames are launched first
+        const int rcf = flush_frames(ctx);
+        if (rcf != RT_OK) return rcf;
+        RT_HIP(ctx, join_aux(ctx));
+        ctx->primary_dirty = true;
+        if (ctx->params.accumulate != 1u)
+            return fail(ctx, RT_E_INVALID, "rt_display: Params.accumulate != 1 never writes the accumulation");
+        if (ctx->k - 1u == 0u || (ctx->k - 1u) * ctx->params.compute_per_frame == 0u)  // D would be 0
+            return fail(ctx, RT_E_INVALID, "rt_display: no frame since the last reset");
+        src = ctx->d_accum;
+        div = (float)((ctx->k - 1u) * ctx->params.compute_per_frame);
+    } else if (dp.source == RT_DISPLAY_DENOISED) {
+        if (ctx->dn_result < 0) return fail(ctx, RT_E_INVALID, "rt_display: no rt_denoise or rt_denoise_temporal yet");
+        src = ctx->d_dn[ctx->dn_result];
+    } else {
+        if (!plane_device) return fail(ctx, RT_E_INVALID, "rt_display: plane_device is NULL");
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, plane_device);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID, "rt_display: plane_device must be device memory of the context's device");
+        }
+        if ((uintptr_t)plane_device & 15u)
+            return fail(ctx, RT_E_INVALID, "rt_display: plane_device must be 16-byte aligned");
+        src = static_cast<const float4*>(plane_device);
+    }
+    int rc;
+    if (!ctx->d_disp_out && (rc = dev_alloc(ctx, &ctx->d_disp_out, ctx->n_pixels))) return rc;
+    if (!ctx->d_disp_meter && (rc = dev_alloc(ctx, &ctx->d_disp_meter, 2u * kDispBins + kDispStateWords))) return rc;
+    uint32_t* bins = ctx->d_disp_meter;
+    uint32_t* kept = bins + kDispBins;
+    uint32_t* state = kept + kDispBins;
+    if (dp.auto_exposure) {
+        RT_HIP(ctx, rt_launch_display_meter(src, ctx->n_pixels, div, bins, ctx->stream));
+        RT_HIP(ctx, rt_launch_display_solve(bins, kept, state, dp.low_permille, dp.high_permille, dp.key, dp.min_exposure,
+                                            dp.max_exposure, dp.adaptation, ctx->disp_exposure_valid, ctx->stream));
+        ctx->disp_exposure_valid = true;
+    }
+    const float iw2 = dp.tone_operator == RT_TONE_REINHARD ? 1.0f / (dp.white * dp.white) : 0.0f;
+    RT_HIP(ctx, rt_launch_display_tone(src, ctx->d_disp_out, ctx->n_pixels, div, dp.auto_exposure ? state : nullptr,
+                                       dp.exposure, iw2, ctx->d_srgb, dp.tone_operator, dp.encode, ctx->stream));
+    ctx->disp_valid = true;
+    return RT_OK;
+}
+
+int rt_read_display(rt_ctx* ctx, uint32_t* rgba8_out) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!ctx->disp_valid) return fail(ctx, RT_E_INVALID, "rt_read_display: no rt_display yet");
+    if (rgba8_out)
+        RT_HIP(ctx, hipMemcpyAsync(rgba8_out, ctx->d_disp_out, ctx->n_pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_copy_display_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!dst_device) return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: dst_device is NULL");
+    if (!ctx->disp_valid) return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: no rt_display yet");
+    {
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, dst_device);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_E_INVALID,
+                        "rt_copy_display_to_device: dst_device is not device memory of the context's device");
+        }
+    }
+    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
+        return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: bytes_per_row < 4 * width");
+    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_disp_out, 4u * (size_t)ctx->width,
+                                 4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
+int rt_display_state(rt_ctx* ctx, float* exposure, uint32_t* histogram, uint64_t* metered) {
+    RT_ENTER_NOFLUSH(ctx);
+    uint32_t words[kDispBins + kDispStateWords] = {};  // kept bins, then the state; zeros before the first auto call
+    if (ctx->d_disp_meter) {
+        RT_HIP(ctx, hipMemcpyAsync(words, ctx->d_disp_meter + kDispBins, sizeof(words), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (exposure) {
+        *exposure = 0.0f;  // no adapted exposure
+        if (ctx->disp_exposure_valid) std::memcpy(exposure, &words[kDispBins], sizeof(float));
+    }
+    if (histogram) std::memcpy(histogram, words, kDispBins * sizeof(uint32_t));
+    if (metered) *metered = (uint64_t)words[kDispBins + 2] | ((uint64_t)words[kDispBins + 3] << 32);
+    return RT_OK;
+}
+
+int rt_display_reset(rt_ctx* ctx) {
+    RT_ENTER_NOFLUSH(ctx);
+    ctx->disp_exposure_valid = false;
     return RT_OK;
 }
 

@@ -614,6 +614,84 @@ class Renderer:
         """``copy_output_to_device`` for the packed denoised output (rt_copy_denoised_to_device)."""
         self._call("rt_copy_denoised_to_device", ctypes.c_void_p(dst_device_ptr), bytes_per_row)
 
+    # ------------------------------------------------------------------ display transform
+    _DISPLAY_SOURCES = {"accumulation": N.RT_DISPLAY_ACCUMULATION, "denoised": N.RT_DISPLAY_DENOISED}
+    _DISPLAY_ENUMS = {"tone_operator": {"linear": N.RT_TONE_LINEAR, "reinhard": N.RT_TONE_REINHARD,
+                                        "aces": N.RT_TONE_ACES},
+                      "encode": {"none": N.RT_ENCODE_NONE, "srgb": N.RT_ENCODE_SRGB}}
+
+    def display(self, source="accumulation", **params):
+        """Radiance to display codes on the device (rt_display; the contract is in include/rt_abi.h):
+        metered auto-exposure, a tone curve and the encode. ``source``: "accumulation" (an observation
+        point: queued frames launch first), "denoised" (what the last ``denoise`` /
+        ``denoise_temporal`` left) or a CUDA float32 torch tensor of height*width*4 values, whose
+        producers on the current torch stream are ordered before the call (through ``stream_handle``,
+        which launches queued frames; the C call with a plane leaves them queued). ``params`` are the fields
+        of rt_display_params (``tone_operator`` and ``encode`` also by name: "linear", "reinhard",
+        "aces"; "none", "srgb"); those left out take rt_display_default_params. Returns the packed
+        image, (H, W) uint32."""
+        p = N.rt_display_params()
+        N.check(None, self._lib.rt_display_default_params(ctypes.byref(p)), self._lib)
+        fields = {name for name, _ in N.rt_display_params._fields_} - {"source"}
+        for key, value in params.items():
+            if key not in fields:
+                raise TypeError(f"display() got an unexpected keyword argument {key!r}")
+            if isinstance(value, str):
+                value = self._DISPLAY_ENUMS[key][value]
+            setattr(p, key, value)
+        if isinstance(source, str):
+            if source not in self._DISPLAY_SOURCES:
+                raise ValueError('source must be "accumulation", "denoised" or a CUDA tensor')
+            p.source = self._DISPLAY_SOURCES[source]
+            self._call("rt_display", ctypes.byref(p), None)
+        else:
+            self._display_plane(source, p)
+        return self.read_display()
+
+    def _display_plane(self, plane, p):
+        import torch
+
+        if (not getattr(plane, "is_cuda", False) or plane.dtype != torch.float32
+                or plane.numel() != self.height * self.width * 4):
+            raise ValueError("a display plane must be a CUDA float32 tensor of height*width*4 values")
+        if plane.device.index != self.device:
+            raise ValueError("a display plane must live on the renderer's device")
+        plane = plane.contiguous()
+        p.source = N.RT_DISPLAY_PLANE
+        # the transform runs on the context's stream: order it after the tensor's producers, and the
+        # caller's stream after it (as _trace_rays_device does)
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=plane.device)
+        cur = torch.cuda.current_stream(plane.device)
+        mine.wait_stream(cur)
+        self._call("rt_display", ctypes.byref(p), ctypes.c_void_p(plane.data_ptr()))
+        cur.wait_stream(mine)
+
+    def read_display(self) -> np.ndarray:
+        """The packed image of the last ``display`` (rt_read_display), (H, W) uint32."""
+        u = np.zeros((self.height, self.width), np.uint32)
+        self._call("rt_read_display", N.ptr(u))
+        return u
+
+    def display_image(self) -> np.ndarray:
+        """The last ``display`` as an (H, W, 4) RGBA8 array (R first), like ``image()``."""
+        return np.ascontiguousarray(self.read_display().view(np.uint8).reshape(self.height, self.width, 4))
+
+    def display_state(self):
+        """(exposure, histogram (256,) uint32, metered) of the last auto-exposure ``display``
+        (rt_display_state); the exposure is 0.0 while there is no adapted exposure."""
+        e, m = ctypes.c_float(), ctypes.c_uint64()
+        hist = np.zeros(256, np.uint32)
+        self._call("rt_display_state", ctypes.byref(e), N.ptr(hist), ctypes.byref(m))
+        return np.float32(e.value), hist, m.value
+
+    def display_reset(self) -> None:
+        """Drop the adapted exposure (rt_display_reset): the next auto-exposure call jumps to its target."""
+        self._call("rt_display_reset")
+
+    def copy_display_to_device(self, dst_device_ptr: int, bytes_per_row: int) -> None:
+        """``copy_output_to_device`` for the display plane (rt_copy_display_to_device)."""
+        self._call("rt_copy_display_to_device", ctypes.c_void_p(dst_device_ptr), bytes_per_row)
+
     def update_texture(self, alignment: int = 256) -> np.ndarray:
         """``Renderer::update_texture`` (src/renderer.rs:254-283), headless: the
         packed output as the Rgba8Unorm display texture the reference copies it
