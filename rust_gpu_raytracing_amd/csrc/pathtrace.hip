@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "rt_path_common.h"
+#include "rt_sphere_walk.h"
 #include "rt_walk.h"
 
 // Analysis builds (tools/isa_loops.py, -DRT_ISA_MARKS) tag kernel regions with an
@@ -251,6 +252,22 @@ struct RootPassCount {
         if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(pm)) {
             atomicAdd(diag + 28, 1ull);
             atomicAdd(diag + 29, (unsigned long long)__popcll(pm));
+        }
+    }
+};
+// Node steps of the sphere walk blocks (rt_sphere_walk.h) in which some lane walks, those lanes, the
+// steps in which some lane reached a leaf and those lanes (words 22-25, as node_visit counts them).
+struct WalkStepCount {
+    unsigned long long* diag;
+    __device__ __forceinline__ void operator()(bool walk, bool at_leaf, uint32_t) const {
+        const uint64_t act = __ballot(walk), lf = __ballot(at_leaf);
+        if (act && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__ballot(true))) {
+            atomicAdd(diag + 22, 1ull);
+            atomicAdd(diag + 23, (unsigned long long)__popcll(act));
+            if (lf) {
+                atomicAdd(diag + 24, 1ull);
+                atomicAdd(diag + 25, (unsigned long long)__popcll(lf));
+            }
         }
     }
 };
@@ -665,7 +682,58 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                     batched = true;
                 }
             }
-            if (!batched && mode == kTrav && (!leaves || ts.pending != kNoLeaf)) {
+            if constexpr (kBlockLeaves<kTris>) {
+                if (mode == kTrav) {
+                    // the block's node steps, branch-free (rt_sphere_walk.h): a lane that waits at a
+                    // leaf or has finished keeps its state through the block's remaining steps
+                    RT_ISA_MARK("node_step");
+                    RT_ISA_MARK("walk_block");
+#ifdef RT_DIAG
+                    const WalkStepCount hook{ka.diag};
+#else
+                    const SphereWalkNoHook hook{};
+#endif
+                    constexpr int kSteps = kTravUnroll<kMode, kTris>;
+                    if (ka.sphere_boxes_ordered)
+                        sphere_walk_block<kSteps, true>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit, ts.node,
+                                                        ts.pending, hook);
+                    else
+                        sphere_walk_block<kSteps, false>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit, ts.node,
+                                                         ts.pending, hook);
+                    RT_ISA_MARK("walk_block_end");
+                    if (ts.pending == kNoLeaf && ts.node >= ka.sphere_nodes) {
+                        ts.phase = 2;
+                        mode = kDone;
+                    }
+                    // the block's group tests: every lane that reached a leaf in it, together
+                    // (the lanes that traversed in this block are the active ones: the ballots count them)
+                    const uint32_t n_wait = (uint32_t)__popcll(__ballot(ts.pending != kNoLeaf));
+                    const uint32_t n_tr = (uint32_t)__popcll(__ballot(true));
+#ifdef RT_DIAG
+                    if (8u * n_wait >= kBlockLeafShare * n_tr) {  // the block group tests and their lanes
+                        const uint64_t gm = __ballot(mode == kTrav && ts.pending != kNoLeaf);
+                        if (gm && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(gm)) {
+                            atomicAdd(ka.diag + 26, 1ull);
+                            atomicAdd(ka.diag + 27, (unsigned long long)__popcll(gm));
+                        }
+                    }
+#endif
+                    if (8u * n_wait >= kBlockLeafShare * n_tr && mode == kTrav && ts.pending != kNoLeaf) {
+                        RT_ISA_MARK("sphere_leaves");
+#ifdef RT_DIAG
+                        test_sphere_group<false>(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph, RootPassCount{ka.diag});
+#else
+                        test_sphere_group(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph);
+#endif
+                        ts.limit = prune_limit(ts);
+                        ts.pending = kNoLeaf;
+                        if (ts.node >= ka.sphere_nodes) {
+                            ts.phase = 2;
+                            mode = kDone;
+                        }
+                    }
+                }
+            } else if (!batched && mode == kTrav && (!leaves || ts.pending != kNoLeaf)) {
                 if (kDeferLeaves<kTris> && leaves) {
                     RT_ISA_MARK("leaf_batch");
                     leaf_step<kTris, (kMode <= 1)>(sv, ka, p.o, p.d, ts);
@@ -702,33 +770,6 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                         (ts.phase == 0) == tri_first) {
                         RT_ISA_MARK("leaf_batch");
                         leaf_step<kTris, (kMode <= 1)>(sv, ka, p.o, p.d, ts);
-                        phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                        if (ts.phase == 2) mode = kDone;
-                    }
-                }
-                if constexpr (kBlockLeaves<kTris>) {
-                    // the block's group tests: every lane that reached a leaf in it, together
-                    // (the lanes that traversed in this block are the active ones: the ballots count them)
-                    const uint32_t n_wait = (uint32_t)__popcll(__ballot(ts.pending != kNoLeaf));
-                    const uint32_t n_tr = (uint32_t)__popcll(__ballot(true));
-#ifdef RT_DIAG
-                    if (8u * n_wait >= kBlockLeafShare * n_tr) {  // the block group tests and their lanes
-                        const uint64_t gm = __ballot(mode == kTrav && ts.pending != kNoLeaf);
-                        if (gm && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(gm)) {
-                            atomicAdd(ka.diag + 26, 1ull);
-                            atomicAdd(ka.diag + 27, (unsigned long long)__popcll(gm));
-                        }
-                    }
-#endif
-                    if (8u * n_wait >= kBlockLeafShare * n_tr && mode == kTrav && ts.pending != kNoLeaf) {
-                        RT_ISA_MARK("sphere_leaves");
-#ifdef RT_DIAG
-                        test_sphere_group<false>(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph, RootPassCount{ka.diag});
-#else
-                        test_sphere_group(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph);
-#endif
-                        ts.limit = prune_limit(ts);
-                        ts.pending = kNoLeaf;
                         phase_end<kTris>(sv, ka, p.o, p.d, ts);
                         if (ts.phase == 2) mode = kDone;
                     }

@@ -3,8 +3,10 @@
 With the default --marks, the kernel is compiled with -DRT_ISA_MARKS, which tags the
 traversal step, the node step, the leaf batch and the shading step with assembly comments
 (RT_ISA_MARK in pathtrace.hip); for each tag the tool reports the innermost loop that
-contains it. The markers are volatile asm statements and can move the schedule a little:
-read the counts as the product build's to within a few instructions.
+contains it, and for a tag with a "<tag>_end" partner (the sphere walk's block of node steps)
+the instructions, branches and labels of the text between the two. The markers are volatile
+asm statements and can move the schedule a little: read the counts as the product build's to
+within a few instructions.
 
 The kernels hold more wave-uniform values (kernel arguments, LDS offsets) than the SGPR
 file; the compiler parks the rest in lanes of a VGPR (v_writelane) and reloads them with
@@ -108,7 +110,30 @@ def analyse(body):
             if inside:
                 best = min(inside, key=lambda lp: lp["last"] - lp["first"])
                 marks.setdefault(mk.group(1), best)
-    return spill, out, total_rl, marks
+    # straight-line regions: from a "<tag>" marker to the next "<tag>_end" marker in the text (the
+    # sphere walk's block of node steps, rt_sphere_walk.h: one region per instantiation)
+    regions = []
+    tags = [(i, MARK.search(ln).group(1)) for i, ln in enumerate(body) if MARK.search(ln)]
+    for k, (i, tag) in enumerate(tags):
+        end = next((j for j, t in tags[k + 1:] if t == tag + "_end"), None)
+        if end is None:
+            continue
+        r = dict(tag=tag, insts=0, valu=0, salu=0, lds=0, waits=0, branches=0, spill_readlanes=0)
+        for j, mn in insts:
+            if not i < j < end:
+                continue
+            r["insts"] += 1
+            r["valu"] += mn.startswith("v_")
+            r["lds"] += mn.startswith("ds_")
+            r["waits"] += mn in ("s_waitcnt", "s_nop")
+            r["branches"] += mn.startswith("s_cbranch") or mn in ("s_branch", "s_setpc_b64")
+            r["salu"] += mn.startswith("s_") and mn not in ("s_waitcnt", "s_nop") and not mn.startswith("s_cbranch") \
+                and mn != "s_branch"
+            rl = READLANE.match(body[j]) if mn == "v_readlane_b32" else None
+            r["spill_readlanes"] += bool(rl and rl.group(1) in spill)
+        r["labels"] = sum(1 for j in range(i + 1, end) if LABEL.match(body[j]))  # 0: nothing jumps into it
+        regions.append(r)
+    return spill, out, total_rl, marks, regions
 
 
 def main():
@@ -129,13 +154,16 @@ def main():
     for name, body in functions(text.splitlines()):
         if args.kernel not in name:
             continue
-        spill, loops, total_rl, marks = analyse(body)
-        short = re.sub(r"_Z19rt_pathtrace_kernelILi(\d)ELj(\d+)ELb([01])ELb([01])EEv10KernelArgs",
-                       r"pathtrace<mode \1, \2 threads, tris \3, wide \4>", name)
+        spill, loops, total_rl, marks, regions = analyse(body)
+        short = re.sub(r"_Z19rt_pathtrace_kernelILi(\d)ELj(\d+)ELb([01])EEv10KernelArgs",
+                       r"pathtrace<mode \1, \2 threads, tris \3>", name)
         print(f"{short}: spill VGPRs {sorted(spill)}, spill reloads in the kernel {total_rl}")
         for tag, lp in sorted(marks.items()):
             print("  {tag:10s} innermost loop around it: insts {insts:5d} valu {valu:5d} spill_readlanes {spill_readlanes:3d}".format(
                 tag=tag, **lp))
+        for r in regions:
+            print("  {tag:10s} region to {tag}_end: insts {insts:4d} valu {valu:4d} salu {salu:3d} lds {lds:3d} waits {waits:3d} "
+                  "branches {branches:2d} labels {labels:2d} spill_readlanes {spill_readlanes:2d}".format(**r))
         for lp in loops if args.all_loops else []:
             if lp["insts"] < args.min_insts:
                 continue
