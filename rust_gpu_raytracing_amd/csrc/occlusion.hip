@@ -3,9 +3,10 @@
 //
 // rt_occlusion_kernel answers "is anything in the way before t_max?" for arbitrary rays: one byte
 // per ray, 1 iff at least one primitive, tested on its own by the reference's test, is accepted at
-// a non-NaN distance t < t_max. It stands on rt_query_kernel's frame (query.hip): one ray per lane,
-// persistent wave64s claiming chunks of rays from one device counter, ballot + mbcnt refill, the
-// three scene placements, the walk of rt_walk.h. What differs:
+// a non-NaN distance t < t_max. It stands on the query kernels' frame (rt_query_frame.h): one ray
+// per lane, persistent wave64s taking chunks of rays (each wave's own first chunk, then claims from
+// one device counter), ballot + mbcnt refill, the three scene placements, the walk of rt_walk.h.
+// What differs from the closest-hit query (query.hip):
 //
 //  * The bound is the search state's seed. Both running bests start at t_max instead of "none":
 //    the walk's own acceptance rule (strictly closer than the best; an equal distance only with a
@@ -23,6 +24,7 @@
 #include <stdint.h>
 
 #include "rt_path_common.h"
+#include "rt_query_frame.h"
 #include "rt_walk.h"
 
 #pragma clang fp contract(off)
@@ -32,41 +34,10 @@ using namespace rtk;
 struct OcclusionArgs {
     const float4* __restrict__ rays;  // rt_occlusion_ray[count]: {origin.xyz, pad}, {direction.xyz, t_max}
     uint8_t* __restrict__ occluded;   // one byte per ray
-    unsigned long long count;
-    unsigned long long* __restrict__ next;  // the chunk counter (zero at launch)
-    uint32_t wave_chunk;                    // rays per claim
-    uint32_t first_chunk;                   // rays of each wave's own first chunk (no claim)
-    unsigned long long claimed_from;        // first ray handed out by the counter: first_chunk x the launch's waves
+    ChunkArgs chunks;
 };
 
 namespace {
-
-// The wave's next chunk of rays, wave-uniform (called by whole waves). The first chunk is the
-// wave's own, by its index in the launch: were it claimed, every resident wave's first claim would
-// queue at one counter address while nothing else runs. After it lane 0 claims from the counter,
-// which hands out the rays from qa.claimed_from on; a launch whose first chunks cover every ray
-// claims nothing. (Reading the counter before claiming, to spare the claim that comes back empty,
-// doubled the run time of 2M rays: a load of that line queues with the claims. DESIGN.md §5.4c.)
-__device__ __forceinline__ void claim_chunk(const OcclusionArgs& qa, uint32_t wave, bool& first,
-                                            unsigned long long& next, unsigned long long& end, bool& dry) {
-    unsigned long long base = qa.count, chunk = qa.wave_chunk;
-    if (first) {
-        base = (unsigned long long)wave * qa.first_chunk;
-        chunk = qa.first_chunk;
-        first = false;
-    }
-    if (base >= qa.count && qa.claimed_from < qa.count) {
-        unsigned long long got = qa.count;
-        if ((threadIdx.x & 63u) == 0) got = atomicAdd(qa.next, (unsigned long long)qa.wave_chunk);
-        const uint32_t b_lo = __builtin_amdgcn_readfirstlane((uint32_t)got);
-        const uint32_t b_hi = __builtin_amdgcn_readfirstlane((uint32_t)(got >> 32));
-        base = qa.claimed_from + (((unsigned long long)b_hi << 32) | b_lo);
-        chunk = qa.wave_chunk;
-    }
-    dry = base >= qa.count;
-    next = dry ? qa.count : base;
-    end = (dry || base + chunk >= qa.count) ? qa.count : base + chunk;
-}
 
 // A candidate was accepted: the walk replaces a best only by a strictly closer candidate (the
 // seed's tie-break position is 0, which no candidate undercuts), so either best below the seed
@@ -161,30 +132,30 @@ __device__ __forceinline__ void occlusion_begin(const SceneView& sv, const Kerne
     phase_setup<kTris>(sv, ka, o, a, phase, ts);
 }
 
+// What ends a step of the any-hit search: a lane's search ends when its walks do or when an
+// occluder is found, whichever is first. (NaN candidates never occlude: the flag is dropped so
+// that phase_end does not sweep for it.)
+struct OccluderEnd {
+    float bound;
+    template <bool kTris>
+    __device__ __forceinline__ void step(const SceneView& sv, const KernelArgs& ka, f3 o, f3 d, TraceState& ts,
+                                         uint32_t& mode) const {
+        ts.nan_hit = false;
+        phase_end<kTris>(sv, ka, o, d, ts);
+        if (ts.phase == 2 || occluder_found(ts, bound)) mode = kLaneDone;
+    }
+};
+
 }  // namespace
 
 template <int kMode, bool kTris, uint32_t kThreads>
 __global__ void __launch_bounds__(kThreads, 1) rt_occlusion_kernel(KernelArgs ka, OcclusionArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint32_t tid = threadIdx.x;
-    SceneView sv{ka.sphere_slots, ka.sphere_orig, ka.sphere_material, ka.sphere_bvh, ka.materials, nullptr,
-                 ka.objects,      nullptr,        ka.tri_bvh,         ka.tri_prims,  kTris ? *ka.tri_extent : 0.0f,
-                 ka.sub_objects};
-    if constexpr (kTris && kMode <= 1) {
-        if (ka.tri_qnodes) {
-            const float4 g0 = ka.tri_qgrid[0], g1 = ka.tri_qgrid[1];
-            if (g0.w != 0.0f) {
-                sv.tri_q = ka.tri_qnodes;
-                sv.qox = g0.x;
-                sv.qoy = g0.y;
-                sv.qoz = g0.z;
-                sv.qsx = g1.x;
-                sv.qsy = g1.y;
-                sv.qsz = g1.z;
-            }
-        }
-    }
-    // The LDS image of the placement, as rt_query_kernel stages it (the same offsets).
+    SceneView sv = global_scene_view<kMode, kTris>(ka, nullptr);
+    // The walk's tables of the LDS image (no record is built: the spheres' materials are left out).
+    // Written out here, not through stage_walk_tables / stage_triangle_tables of rt_query_frame.h:
+    // with them the (1, triangles) instance has 34 SGPR spills instead of 31.
     if constexpr (kMode >= 1) {
         float4* l_sph = reinterpret_cast<float4*>(lds);
         RtObject* l_obj = reinterpret_cast<RtObject*>(lds + ka.lds_obj_offset);
@@ -223,30 +194,11 @@ __global__ void __launch_bounds__(kThreads, 1) rt_occlusion_kernel(KernelArgs ka
     unsigned long long ray = 0;
     f3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 0.f);
     float bound = 0.0f;  // the seed: min(t_max, F32_MAX), or 0 for a t_max that nothing is closer than
-    TraceState ts;
-    ts.inv = mk(0.f, 0.f, 0.f);
-    ts.a4 = ts.a2 = 0.f;
-    ts.node = 0;
-    ts.phase = 2;
-    ts.pending = kNoLeaf;
-    ts.nan_hit = false;
-    ts.sph = SphereHit{0.0f, 0u, 0u};
-    ts.tri = TriHit{0.0f, 0u, 0u, 0u, false};
+    TraceState ts = idle_trace_state(0.0f);
 
-    // A lane's search ends when its walks do or when an occluder is found, whichever is first.
-    // (NaN candidates never occlude: the flag is dropped so that phase_end does not sweep for it.)
-    auto step_end = [&]() {
-        ts.nan_hit = false;
-        phase_end<kTris>(sv, ka, o, d, ts);
-        if (ts.phase == 2 || occluder_found(ts, bound)) mode = kDone;
-    };
-
-    // The wave's chunk [next, end) of the ray array, wave-uniform.
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / 64u) + (tid >> 6));
-    bool first = true;
-    unsigned long long next = 0, end = 0;
-    bool dry = false;  // no rays are left for this wave
-    claim_chunk(qa, wave, first, next, end, dry);
+    const uint32_t wave = wave_in_launch<kThreads>();
+    WaveChunk c{0, 0, true, false};
+    claim_chunk(qa.chunks, wave, c);
 
     while (true) {
         // 1. The bytes of the lanes whose search has finished.
@@ -257,13 +209,12 @@ __global__ void __launch_bounds__(kThreads, 1) rt_occlusion_kernel(KernelArgs ka
         // 2. Refill: idle lanes take the chunk's next rays, in order.
         while (true) {
             const uint64_t need = __ballot(mode == kIdle);
-            if (need == 0 || dry) break;
-            const uint32_t avail = (uint32_t)(end - next);
+            if (need == 0 || c.dry) break;
+            const uint32_t avail = (uint32_t)(c.end - c.next);
             if (mode == kIdle) {
-                const uint32_t rank =
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                const uint32_t rank = rank_among(need);
                 if (rank < avail) {
-                    ray = next + rank;
+                    ray = c.next + rank;
                     const float4 r0 = qa.rays[2ull * ray], r1 = qa.rays[2ull * ray + 1ull];
                     o = mk(r0.x, r0.y, r0.z);
                     d = mk(r1.x, r1.y, r1.z);
@@ -272,8 +223,8 @@ __global__ void __launch_bounds__(kThreads, 1) rt_occlusion_kernel(KernelArgs ka
                     mode = kSetup;
                 }
             }
-            next += min((uint32_t)__popcll(need), avail);
-            if (next == end) claim_chunk(qa, wave, first, next, end, dry);
+            c.next += min((uint32_t)__popcll(need), avail);
+            if (c.next == c.end) claim_chunk(qa.chunks, wave, c);
         }
         // 3. Start the search of every lane that took a ray.
         if (mode == kSetup) {
@@ -285,111 +236,45 @@ __global__ void __launch_bounds__(kThreads, 1) rt_occlusion_kernel(KernelArgs ka
                 mode = kDone;
             }
         }
-        if (__ballot(mode != kIdle) == 0 && dry) break;
-        // 4. Traverse, as rt_query_kernel does: lanes whose search finishes wait until at most
-        // trav_threshold lanes still traverse, then the wave writes their bytes and refills them
-        // together; with no rays left it traverses to the end.
-        const uint32_t thresh = dry ? 0u : ka.trav_threshold;
-        while (true) {
-            const uint64_t trav = __ballot(mode == kTrav);
-            const uint32_t n_trav = (uint32_t)__popcll(trav);
-            if (n_trav <= thresh || trav == 0) break;
-            bool leaves = false;
-            if constexpr (kDeferLeaves<kTris> && !kFusedLeaves<kMode, kTris>) {
-                const uint32_t n_pend = (uint32_t)__popcll(__ballot(mode == kTrav && ts.pending != kNoLeaf));
-                leaves = 8u * n_pend >= ka.leaf_batch * n_trav;
-            }
-            bool batched = false;
-            if constexpr (kCoopLeaves<kMode, kTris>) {
-                if (leaves && ka.tri_leaftris) {  // the wave's deferred leaves, cooperatively
-                    const bool act = mode == kTrav && ts.pending != kNoLeaf;
-                    coop_leaf_batch(sv, ka, o, d, ts, act, lds);
-                    if (act) step_end();
-                    batched = true;
-                }
-            }
-            if (!batched && mode == kTrav && (!leaves || ts.pending != kNoLeaf)) {
-                if (kDeferLeaves<kTris> && leaves) {
-                    leaf_step<kTris, (kMode <= 1)>(sv, ka, o, d, ts);
-                } else {
-                    node_step<kTris, kCertWalk<kMode>>(sv, ka, o, d, ts);
-                }
-                step_end();
-                if (!(kDeferLeaves<kTris> && leaves)) {
-#pragma unroll
-                    for (int k = 1; k < kTravUnroll<kMode, kTris>; ++k) {
-                        if (mode == kTrav) {
-                            node_step<kTris, kCertWalk<kMode>>(sv, ka, o, d, ts);
-                            step_end();
-                        }
-                    }
-                }
-                if constexpr (kFusedLeaves<kMode, kTris>) {
-                    // the leaf batch after the block's node steps: one kind of leaf per batch
-                    const uint64_t mt = __ballot(mode == kTrav && ts.pending != kNoLeaf && ts.phase == 0);
-                    const uint64_t ms = __ballot(mode == kTrav && ts.pending != kNoLeaf && ts.phase != 0);
-                    const uint32_t n_p = (uint32_t)__popcll(mt | ms);
-                    const uint32_t n_t = (uint32_t)__popcll(__ballot(mode == kTrav));
-                    const bool tri_first = __popcll(mt) >= __popcll(ms);
-                    if (8u * n_p >= ka.leaf_batch * n_t && mode == kTrav && ts.pending != kNoLeaf &&
-                        (ts.phase == 0) == tri_first) {
-                        leaf_step<kTris, (kMode <= 1)>(sv, ka, o, d, ts);
-                        step_end();
-                    }
-                }
-                if constexpr (kBlockLeaves<kTris>) {
-                    // the block's group tests: every lane that reached a leaf in it, together
-                    const uint32_t n_wait = (uint32_t)__popcll(__ballot(ts.pending != kNoLeaf));
-                    const uint32_t n_tr = (uint32_t)__popcll(__ballot(true));
-                    if (8u * n_wait >= kBlockLeafShare * n_tr && mode == kTrav && ts.pending != kNoLeaf) {
-                        test_sphere_group(sv, ts.pending, o, d, ts.a4, ts.a2, ts.sph);
-                        ts.limit = prune_limit(ts);
-                        ts.pending = kNoLeaf;
-                        step_end();
-                    }
-                }
-            }
-        }
+        if (__ballot(mode != kIdle) == 0 && c.dry) break;
+        // 4. Traverse (query_traverse): finished lanes wait for the wave, which then writes their
+        // bytes and refills them together; with no rays left it traverses to the end.
+        take_lane_walk(query_traverse<kMode, kTris, false>(sv, ka, o, d, lane_walk(ts, mode), c.dry, lds, OccluderEnd{bound}),
+                       ts, mode);
     }
 }
 
-// Workgroup size by placement, as the closest-hit query's (query.hip).
-uint32_t rt_occlusion_threads(int mode) { return mode == 0 ? 256u : 1024u; }
+// The instances, (mode, triangles, threads): f(kernel, threads) for the one of (mode, tris). The
+// workgroup sizes are the closest-hit query's (query.hip).
+template <class F>
+static hipError_t with_occlusion_instance(int mode, bool tris, F f) {
+    if (mode == 0 && tris) return f(&rt_occlusion_kernel<0, true, 256>, 256u);
+    if (mode == 1 && tris) return f(&rt_occlusion_kernel<1, true, 1024>, 1024u);
+    if (mode == 2 && tris) return f(&rt_occlusion_kernel<2, true, 1024>, 1024u);
+    if (mode == 0 && !tris) return f(&rt_occlusion_kernel<0, false, 256>, 256u);
+    if (mode == 1 && !tris) return f(&rt_occlusion_kernel<1, false, 1024>, 1024u);
+    return hipErrorInvalidValue;
+}
 
-// (mode, triangles, threads)
-#define RT_FOR_EACH_OCCLUSION(X) \
-    X(0, true, 256) X(1, true, 1024) X(2, true, 1024) X(0, false, 256) X(1, false, 1024)
+// (0 for a (mode, tris) without an instance, as rt_query_threads)
+uint32_t rt_occlusion_threads(int mode, bool tris) {
+    uint32_t threads = 0;
+    (void)with_occlusion_instance(mode, tris, [&](auto, uint32_t t) { return threads = t, hipSuccess; });
+    return threads;
+}
 
-// Resident workgroups per CU of the instance at this dynamic LDS size (0: it does not fit).
 hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
-#define RT_OOCC(M, TR, T)                                                                                \
-    if (mode == M && tris == TR) {                                                                          \
-        const void* fn = reinterpret_cast<const void*>(&rt_occlusion_kernel<M, TR, T>);                  \
-        if (lds_bytes > 64u * 1024u) {                                                                      \
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-            if (e != hipSuccess) return e;                                                                  \
-        }                                                                                                   \
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, rt_occlusion_kernel<M, TR, T>, T, \
-                                                            lds_bytes);                                    \
-    }
-    RT_FOR_EACH_OCCLUSION(RT_OOCC)
-#undef RT_OOCC
-    return hipErrorInvalidValue;
+    return with_occlusion_instance(
+        mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
 }
 
-hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
-                               uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream) {
-    if (blocks == 0 || count == 0) return hipSuccess;
-    const unsigned long long waves = (unsigned long long)blocks * (rt_occlusion_threads(mode) / 64u);
-    const OcclusionArgs qa{static_cast<const float4*>(rays), static_cast<uint8_t*>(occluded), count, counter,
-                           wave_chunk, first_chunk, waves * first_chunk};
-#define RT_OLAUNCH(M, TR, T)                                                                                  \
-    if (mode == M && tris == TR) {                                                                               \
-        hipLaunchKernelGGL((rt_occlusion_kernel<M, TR, T>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
-        return hipGetLastError();                                                                                \
-    }
-    RT_FOR_EACH_OCCLUSION(RT_OLAUNCH)
-#undef RT_OLAUNCH
-    return hipErrorInvalidValue;
+                               hipStream_t stream) {
+    if (s.blocks == 0 || count == 0) return hipSuccess;
+    return with_occlusion_instance(mode, tris, [&](auto kernel, uint32_t t) {
+        const OcclusionArgs qa{static_cast<const float4*>(rays), static_cast<uint8_t*>(occluded),
+                               chunk_args(count, counter, s, t)};
+        return query_launch_of(kernel, t, s.blocks, lds_bytes, stream, ka, qa);
+    });
 }

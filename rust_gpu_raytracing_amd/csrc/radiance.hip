@@ -4,8 +4,8 @@
 // rt_radiance_kernel answers "how much light arrives along this ray?" for arbitrary rays: per_pixel
 // of the reference (compute_shader.wgsl:210-314) with the camera origin, the pixel's direction and
 // the pixel index of the seed taken from a 32-B record, summed over `samples` samples. It stands on
-// rt_query_kernel's frame (query.hip) -- one ray per lane, persistent wave64s claiming chunks of
-// rays, ballot + mbcnt refill, the three scene placements, the walk of rt_walk.h -- and on the path
+// the query kernels' frame (rt_query_frame.h) -- one ray per lane, persistent wave64s taking chunks
+// of rays, ballot + mbcnt refill, the three scene placements, the walk of rt_walk.h -- and on the path
 // kernel's shading (rt_path_common.h: trace_end, shade, Path). Nothing of the framebuffer is read
 // or written. What differs from the closest-hit query:
 //
@@ -21,7 +21,7 @@
 //    constants and 1x1 texels, and the sRGB table are staged at the path kernel's offsets
 //    (shade<true>); mode 0 reads materials and the table from global memory (shade<false>). Every
 //    placement returns the same bits.
-//  * Each wave's first chunk is its own, by its index in the launch, as in rt_occlusion_kernel.
+//  * Each wave's first chunk is its own, by its index in the launch (claim_chunk).
 //  * Counted ray segments (the rule of rt_ray_count: one per trace_ray call) are summed per lane,
 //    reduced once per wave at exit and added to the caller's counter with one atomic per wave.
 //
@@ -61,6 +61,7 @@
 #include <stdint.h>
 
 #include "rt_path_common.h"
+#include "rt_query_frame.h"
 #include "rt_walk.h"
 
 #pragma clang fp contract(off)
@@ -70,6 +71,8 @@ using namespace rtk;
 struct RadianceArgs {
     const float4* __restrict__ rays;  // rt_radiance_ray[count]: {origin.xyz, stream}, {direction.xyz, pad}
     float4* __restrict__ radiance;    // one float4 per ray
+    // the fields of ChunkArgs (rt_query_frame.h: rt_launch_radiance fills them from chunk_args), in
+    // the order this kernel's registers were tuned at
     unsigned long long count;
     unsigned long long* __restrict__ next;      // the chunk counter (zero at launch)
     unsigned long long* __restrict__ segments;  // counted ray segments, added to (null: not counted)
@@ -81,34 +84,6 @@ struct RadianceArgs {
     uint32_t stripes;                           // kGather: stripes per point, min(samples, 64)
 };
 
-namespace {
-
-// The wave's next chunk of rays, wave-uniform (called by whole waves): rt_occlusion_kernel's
-// schedule (occlusion.hip). The first chunk is the wave's own, by its index in the launch; after
-// it lane 0 claims from the counter, which hands out the rays from qa.claimed_from on.
-__device__ __forceinline__ void claim_chunk(const RadianceArgs& qa, uint32_t wave, bool& first,
-                                            unsigned long long& next, unsigned long long& end, bool& dry) {
-    unsigned long long base = qa.count, chunk = qa.wave_chunk;
-    if (first) {
-        base = (unsigned long long)wave * qa.first_chunk;
-        chunk = qa.first_chunk;
-        first = false;
-    }
-    if (base >= qa.count && qa.claimed_from < qa.count) {
-        unsigned long long got = qa.count;
-        if ((threadIdx.x & 63u) == 0) got = atomicAdd(qa.next, (unsigned long long)qa.wave_chunk);
-        const uint32_t b_lo = __builtin_amdgcn_readfirstlane((uint32_t)got);
-        const uint32_t b_hi = __builtin_amdgcn_readfirstlane((uint32_t)(got >> 32));
-        base = qa.claimed_from + (((unsigned long long)b_hi << 32) | b_lo);
-        chunk = qa.wave_chunk;
-    }
-    dry = base >= qa.count;
-    next = dry ? qa.count : base;
-    end = (dry || base + chunk >= qa.count) ? qa.count : base + chunk;
-}
-
-}  // namespace
-
 // kGather: the path kernel of a gather query (the contract above). A "ray" is then a (point,
 // stripe) item: qa.rays holds rt_gather_point records, qa.count the launch's items (points x
 // qa.stripes, below 2^32), and qa.radiance the partials, 64 float4 per point.
@@ -116,79 +91,15 @@ template <int kMode, bool kTris, uint32_t kThreads, bool kGather = false>
 __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka, RadianceArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool kAux = kMode >= 1;
-    const uint32_t tid = threadIdx.x;
-    SceneView sv{ka.sphere_slots, ka.sphere_orig, ka.sphere_material, ka.sphere_bvh, ka.materials, nullptr,
-                 ka.objects,      ka.srgb,        ka.tri_bvh,         ka.tri_prims,  kTris ? *ka.tri_extent : 0.0f,
-                 ka.sub_objects};
-    if constexpr (kTris && kMode <= 1) {
-        if (ka.tri_qnodes) {
-            const float4 g0 = ka.tri_qgrid[0], g1 = ka.tri_qgrid[1];
-            if (g0.w != 0.0f) {
-                sv.tri_q = ka.tri_qnodes;
-                sv.qox = g0.x;
-                sv.qoy = g0.y;
-                sv.qoz = g0.z;
-                sv.qsx = g1.x;
-                sv.qsy = g1.y;
-                sv.qsz = g1.z;
-            }
-        }
-    }
-    // The path kernel's LDS image at the same offsets, without the camera block.
+    // The path kernel's LDS image without the camera block: what the walk, the record and shading
+    // read.
+    SceneView sv = global_scene_view<kMode, kTris>(ka, ka.srgb);
     if constexpr (kMode >= 1) {
-        float4* l_sph = reinterpret_cast<float4*>(lds);
-        RtMaterial* l_mat = reinterpret_cast<RtMaterial*>(lds + ka.lds_mat_offset);
-        float4* l_aux = reinterpret_cast<float4*>(lds + ka.lds_mat_aux_offset);
-        RtObject* l_obj = reinterpret_cast<RtObject*>(lds + ka.lds_obj_offset);
-        uint32_t* l_orig = reinterpret_cast<uint32_t*>(lds + ka.lds_orig_offset);
-        uint32_t* l_smat = reinterpret_cast<uint32_t*>(lds + ka.lds_smat_offset);
-        float4* l_nodes = reinterpret_cast<float4*>(lds + ka.lds_nodes_offset);
-        float* l_srgb = reinterpret_cast<float*>(lds + ka.lds_srgb_offset);
-        for (uint32_t i = tid; i < ka.sphere_slot_count; i += kThreads) {
-            l_sph[i] = ka.sphere_slots[i];
-            l_orig[i] = ka.sphere_orig[i];
-        }
-        for (uint32_t i = tid; i < ka.sphere_count; i += kThreads) l_smat[i] = ka.sphere_material[i];
-        for (uint32_t i = tid; i < 2u * ka.sphere_nodes; i += kThreads) l_nodes[i] = ka.sphere_bvh[i];
-        for (uint32_t i = tid; i < ka.material_count; i += kThreads) {
-            const RtMaterial m = ka.materials[i];
-            l_mat[i] = m;
-            // shade()'s glass constants, by the same f32 operations (:320, :328-334, :307)
-            const float ior_front = 1.0f / m.refraction_index;
-            float r0f = (1.0f - ior_front) / (1.0f + ior_front);
-            float r0b = (1.0f - m.refraction_index) / (1.0f + m.refraction_index);
-            r0f = r0f * r0f;
-            r0b = r0b * r0b;
-            l_aux[2u * i] = make_float4(ior_front, r0f, r0b, div_const(m.roughness, 10.0f, kInv10));
-            // the decoded texel a 1x1 texture layer gives every hit (sample_texture, :26-32)
-            const f4 c = decode_texel(ka.textures[min(m.texture_index, ka.tex_layers - 1u)], ka.srgb);
-            l_aux[2u * i + 1u] = make_float4(c.x, c.y, c.z, c.w);
-        }
-        if constexpr (kTris)
-            for (uint32_t i = tid; i < ka.object_count; i += kThreads) l_obj[i] = ka.objects[i];
-        for (uint32_t i = tid; i < 256u; i += kThreads) l_srgb[i] = ka.srgb[i];
-        sv.sph = l_sph;
-        sv.orig = l_orig;
-        sv.sph_mat = l_smat;
-        sv.nodes = l_nodes;
-        sv.mat = l_mat;
-        sv.mat_aux = l_aux;
-        sv.obj = l_obj;
-        sv.srgb = l_srgb;
+        sv = stage_walk_tables<kTris, kThreads>(ka, lds, sv);
+        sv = stage_sphere_materials<kThreads>(ka, lds, sv);
+        sv = stage_shading_tables<kThreads>(ka, lds, sv);
     }
-    if constexpr (kMode == 2) {
-        float4* l_tn = reinterpret_cast<float4*>(lds + ka.lds_tri_nodes_offset);
-        uint4* l_tp = reinterpret_cast<uint4*>(lds + ka.lds_tri_prims_offset);
-        for (uint32_t i = tid; i < 2u * ka.tri_nodes; i += kThreads) l_tn[i] = ka.tri_bvh[i];
-        for (uint32_t i = tid; i < ka.tri_prim_count; i += kThreads) l_tp[i] = ka.tri_prims[i];
-        sv.tri_nodes = l_tn;
-        sv.tri_prims = l_tp;
-        if (ka.lds_sub_offset) {
-            RtSubObject* l_sub = reinterpret_cast<RtSubObject*>(lds + ka.lds_sub_offset);
-            for (uint32_t i = tid; i < ka.sub_object_count; i += kThreads) l_sub[i] = ka.sub_objects[i];
-            sv.sub = l_sub;
-        }
-    }
+    if constexpr (kMode == 2) sv = stage_triangle_tables<kThreads>(ka, lds, sv);
     if constexpr (kMode >= 1) __syncthreads();
 
     // Lane states. A lane owns one ray at a time and one segment of its current sample's path.
@@ -202,15 +113,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
     p.o = p.d = mk(0.f, 0.f, 0.f);
     p.light = p.contrib = f4{0.f, 0.f, 0.f, 0.f};
     p.seed = p.bounce = 0;
-    TraceState ts;
-    ts.inv = mk(0.f, 0.f, 0.f);
-    ts.a4 = ts.a2 = 0.f;
-    ts.node = 0;
-    ts.phase = 2;
-    ts.pending = kNoLeaf;
-    ts.nan_hit = false;
-    ts.sph = SphereHit{kF32Max, 0u, 0u};
-    ts.tri = TriHit{kF32Max, 0u, 0u, 0u, false};
+    TraceState ts = idle_trace_state(kF32Max);
 
     // Sample `sample` of the lane's ray: the record is read again (two 16-B loads that hit the
     // cache) instead of holding origin, direction and stream in 7 registers through every walk.
@@ -234,12 +137,9 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
         mode = kSetup;
     };
 
-    // The wave's chunk [next, end) of the ray array, wave-uniform.
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / 64u) + (tid >> 6));
-    bool first = true;
-    unsigned long long next = 0, end = 0;
-    bool dry = false;  // no rays are left for this wave
-    claim_chunk(qa, wave, first, next, end, dry);
+    const uint32_t wave = wave_in_launch<kThreads>();
+    WaveChunk c{0, 0, true, false};
+    claim_chunk(qa, wave, c);
 
     while (true) {
         // 1. Shade the lanes whose walk has finished (:228-311). A path that ends adds its light
@@ -273,26 +173,25 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
         // 2. Refill: idle lanes take the chunk's next rays, in order.
         while (true) {
             const uint64_t need = __ballot(mode == kIdle);
-            if (need == 0 || dry) break;
-            const uint32_t avail = (uint32_t)(end - next);
+            if (need == 0 || c.dry) break;
+            const uint32_t avail = (uint32_t)(c.end - c.next);
             if (mode == kIdle) {
-                const uint32_t rank =
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                const uint32_t rank = rank_among(need);
                 if (rank < avail) {
                     if constexpr (kGather) {
-                        const uint32_t item = (uint32_t)(next + rank), point = item / qa.stripes;
+                        const uint32_t item = (uint32_t)(c.next + rank), point = item / qa.stripes;
                         sample = item - point * qa.stripes;
                         ray = (unsigned long long)point * 64u + sample;
                     } else {
-                        ray = next + rank;
+                        ray = c.next + rank;
                         sample = 0;
                     }
                     sum = make_float4(0.f, 0.f, 0.f, 0.f);
                     begin_sample();
                 }
             }
-            next += min((uint32_t)__popcll(need), avail);
-            if (next == end) claim_chunk(qa, wave, first, next, end, dry);
+            c.next += min((uint32_t)__popcll(need), avail);
+            if (c.next == c.end) claim_chunk(qa, wave, c);
         }
         // 3. Start the next segment of every lane that has one (ka.bounces >= 1: a path that
         // reached the limit ended in shade).
@@ -300,93 +199,11 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
             trace_begin<kTris>(sv, ka, p.o, p.d, ts);
             mode = ts.phase == 2 ? kDone : kTrav;
         }
-        if (__ballot(mode != kIdle) == 0 && dry) break;
-        // 4. Traverse, as the path kernel does (pathtrace.hip, step 4): lanes whose walk finishes
-        // wait until at most trav_threshold lanes still traverse, then the wave shades and refills
-        // them together. With no rays left the wave traverses to the end before it shades, except
-        // the instances whose triangle accelerator stays in global memory, which decouple the
-        // drain by the path kernel's rule (drain_threshold, drain_min_steps).
-        uint32_t thresh = dry ? 0u : ka.trav_threshold;
-        uint32_t n_active = 64u, min_steps = 0u;
-        if constexpr (kDrainDecouple<kMode, kTris>) {
-            if (dry) {
-                thresh = ka.drain_threshold;
-                n_active = (uint32_t)__popcll(__ballot(mode == kTrav || mode == kDone));
-                min_steps = ka.drain_min_steps;
-            }
-        }
-        while (true) {
-            const uint64_t trav = __ballot(mode == kTrav);
-            const uint32_t n_trav = (uint32_t)__popcll(trav);
-            if constexpr (kDrainDecouple<kMode, kTris>) {
-                if (trav == 0 || (n_trav <= thresh && n_trav < n_active && min_steps == 0)) break;
-                min_steps -= min_steps != 0;
-            } else {
-                if (n_trav <= thresh || trav == 0) break;
-            }
-            bool leaves = false;
-            if constexpr (kDeferLeaves<kTris> && !kFusedLeaves<kMode, kTris>) {
-                const uint32_t n_pend = (uint32_t)__popcll(__ballot(mode == kTrav && ts.pending != kNoLeaf));
-                leaves = 8u * n_pend >= ka.leaf_batch * n_trav;
-            }
-            bool batched = false;
-            if constexpr (kCoopLeaves<kMode, kTris>) {
-                if (leaves && ka.tri_leaftris) {  // the wave's deferred leaves, cooperatively
-                    const bool act = mode == kTrav && ts.pending != kNoLeaf;
-                    coop_leaf_batch(sv, ka, p.o, p.d, ts, act, lds);
-                    if (act) {
-                        phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                        if (ts.phase == 2) mode = kDone;
-                    }
-                    batched = true;
-                }
-            }
-            if (!batched && mode == kTrav && (!leaves || ts.pending != kNoLeaf)) {
-                if (kDeferLeaves<kTris> && leaves) {
-                    leaf_step<kTris, (kMode <= 1)>(sv, ka, p.o, p.d, ts);
-                } else {
-                    node_step<kTris, kCertWalk<kMode>>(sv, ka, p.o, p.d, ts);
-                }
-                phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                if (ts.phase == 2) mode = kDone;
-                if (!(kDeferLeaves<kTris> && leaves)) {
-#pragma unroll
-                    for (int k = 1; k < kTravUnroll<kMode, kTris>; ++k) {
-                        if (mode == kTrav) {
-                            node_step<kTris, kCertWalk<kMode>>(sv, ka, p.o, p.d, ts);
-                            phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                            if (ts.phase == 2) mode = kDone;
-                        }
-                    }
-                }
-                if constexpr (kFusedLeaves<kMode, kTris>) {
-                    // the leaf batch after the block's node steps: one kind of leaf per batch
-                    const uint64_t mt = __ballot(mode == kTrav && ts.pending != kNoLeaf && ts.phase == 0);
-                    const uint64_t ms = __ballot(mode == kTrav && ts.pending != kNoLeaf && ts.phase != 0);
-                    const uint32_t n_p = (uint32_t)__popcll(mt | ms);
-                    const uint32_t n_t = (uint32_t)__popcll(__ballot(mode == kTrav));
-                    const bool tri_first = __popcll(mt) >= __popcll(ms);
-                    if (8u * n_p >= ka.leaf_batch * n_t && mode == kTrav && ts.pending != kNoLeaf &&
-                        (ts.phase == 0) == tri_first) {
-                        leaf_step<kTris, (kMode <= 1)>(sv, ka, p.o, p.d, ts);
-                        phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                        if (ts.phase == 2) mode = kDone;
-                    }
-                }
-                if constexpr (kBlockLeaves<kTris>) {
-                    // the block's group tests: every lane that reached a leaf in it, together
-                    const uint32_t n_wait = (uint32_t)__popcll(__ballot(ts.pending != kNoLeaf));
-                    const uint32_t n_tr = (uint32_t)__popcll(__ballot(true));
-                    if (8u * n_wait >= kBlockLeafShare * n_tr && mode == kTrav && ts.pending != kNoLeaf) {
-                        test_sphere_group(sv, ts.pending, p.o, p.d, ts.a4, ts.a2, ts.sph);
-                        ts.limit = prune_limit(ts);
-                        ts.pending = kNoLeaf;
-                        phase_end<kTris>(sv, ka, p.o, p.d, ts);
-                        if (ts.phase == 2) mode = kDone;
-                    }
-                }
-            }
-        }
+        if (__ballot(mode != kIdle) == 0 && c.dry) break;
+        // 4. Traverse (query_traverse, with the drain rule): finished lanes wait for the wave, which
+        // then shades and refills them together.
+        take_lane_walk(query_traverse<kMode, kTris, true>(sv, ka, p.o, p.d, lane_walk(ts, mode), c.dry, lds, WalkEnd{}), ts,
+                       mode);
     }
     // The wave's counted segments: one reduction and one atomic per wave (the loop's exit is
     // wave-uniform, so all 64 lanes are here).
@@ -394,7 +211,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
         unsigned long long total = segs;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
-        if ((tid & 63u) == 0 && total != 0) atomicAdd(qa.segments, total);
+        if ((threadIdx.x & 63u) == 0 && total != 0) atomicAdd(qa.segments, total);
     }
 }
 
@@ -419,59 +236,55 @@ __global__ void __launch_bounds__(kResolveThreads) rt_gather_resolve_kernel(cons
     if (lane == 0) radiance[point] = v;
 }
 
-// Workgroup size by placement. The global-memory instance has no image to share: small workgroups,
-// as the closest-hit query's. The staged instances share one image among as many waves as their
-// registers allow without spilling: the walks from global memory with the shading state live need
-// about 150 VGPRs (the path kernel's figure), which 16 waves per workgroup (128 each) would spill.
-uint32_t rt_radiance_threads(int mode, bool tris) { return mode == 0 ? 256u : (tris && mode == 1) ? 512u : 1024u; }
-
-// (mode, triangles, threads); each also as the gather instance
-#define RT_FOR_EACH_RADIANCE(X) \
-    X(0, true, 256) X(1, true, 512) X(2, true, 1024) X(0, false, 256) X(1, false, 1024)
-
-template <class K>
-static hipError_t radiance_occupancy_of(K kernel, uint32_t threads, size_t lds_bytes, int* blocks_per_cu) {
-    if (lds_bytes > 64u * 1024u) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kernel, threads, lds_bytes);
+// The instances, (mode, triangles, threads), each also as the gather instance: f(kernel, threads)
+// for the one of (mode, tris, gather). Workgroup size by placement: the global-memory instance has
+// no image to share: small workgroups, as the closest-hit query's. The staged instances share one
+// image among as many waves as their registers allow without spilling: the walks from global
+// memory with the shading state live need about 150 VGPRs (the path kernel's figure), which 16
+// waves per workgroup (128 each) would spill.
+template <bool kGather, class F>
+static hipError_t with_radiance_instance(int mode, bool tris, F f) {
+    if (mode == 0 && tris) return f(&rt_radiance_kernel<0, true, 256, kGather>, 256u);
+    if (mode == 1 && tris) return f(&rt_radiance_kernel<1, true, 512, kGather>, 512u);
+    if (mode == 2 && tris) return f(&rt_radiance_kernel<2, true, 1024, kGather>, 1024u);
+    if (mode == 0 && !tris) return f(&rt_radiance_kernel<0, false, 256, kGather>, 256u);
+    if (mode == 1 && !tris) return f(&rt_radiance_kernel<1, false, 1024, kGather>, 1024u);
+    return hipErrorInvalidValue;
 }
 
-// Resident workgroups per CU of the instance at this dynamic LDS size (0: it does not fit).
-hipError_t rt_radiance_occupancy(int mode, bool tris, bool gather, size_t lds_bytes, int* blocks_per_cu) {
-#define RT_ROCC(M, TR, T)                                                                                  \
-    if (mode == M && tris == TR)                                                                           \
-        return gather ? radiance_occupancy_of(&rt_radiance_kernel<M, TR, T, true>, T, lds_bytes, blocks_per_cu) \
-                      : radiance_occupancy_of(&rt_radiance_kernel<M, TR, T, false>, T, lds_bytes, blocks_per_cu);
-    RT_FOR_EACH_RADIANCE(RT_ROCC)
-#undef RT_ROCC
-    return hipErrorInvalidValue;
+// (0 for a (mode, tris) without an instance, as rt_query_threads)
+uint32_t rt_radiance_threads(int mode, bool tris) {
+    uint32_t threads = 0;
+    (void)with_radiance_instance<false>(mode, tris, [&](auto, uint32_t t) { return threads = t, hipSuccess; });
+    return threads;
+}
+
+hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return with_radiance_instance<false>(
+        mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
+}
+
+hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return with_radiance_instance<true>(
+        mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
 }
 
 // `stripes` 0: a radiance query of `count` rays. Otherwise the path kernel of a gather query:
 // `rays` holds rt_gather_point records, `count` is the launch's items (points x stripes) and
 // `radiance` receives the partials, 64 float4 per point.
-hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                               const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
-                              unsigned long long* segments, uint32_t wave_chunk, uint32_t first_chunk,
-                              uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream) {
-    if (blocks == 0 || count == 0) return hipSuccess;
-    const unsigned long long waves = (unsigned long long)blocks * (rt_radiance_threads(mode, tris) / 64u);
-    const RadianceArgs qa{static_cast<const float4*>(rays), static_cast<float4*>(radiance), count, counter, segments,
-                          wave_chunk, first_chunk, waves * first_chunk, first_sample, samples, stripes};
-#define RT_RLAUNCH(M, TR, T)                                                                                  \
-    if (mode == M && tris == TR) {                                                                            \
-        if (stripes)                                                                                          \
-            hipLaunchKernelGGL((rt_radiance_kernel<M, TR, T, true>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((rt_radiance_kernel<M, TR, T, false>), dim3(blocks), dim3(T), lds_bytes, stream, ka, qa); \
-        return hipGetLastError();                                                                             \
-    }
-    RT_FOR_EACH_RADIANCE(RT_RLAUNCH)
-#undef RT_RLAUNCH
-    return hipErrorInvalidValue;
+                              unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
+                              hipStream_t stream) {
+    if (s.blocks == 0 || count == 0) return hipSuccess;
+    auto launch = [&](auto kernel, uint32_t t) {
+        const ChunkArgs ca = chunk_args(count, counter, s, t);
+        const RadianceArgs qa{static_cast<const float4*>(rays), static_cast<float4*>(radiance),
+                              ca.count, ca.next, segments, ca.wave_chunk, ca.first_chunk, ca.claimed_from,
+                              first_sample, samples, stripes};
+        return query_launch_of(kernel, t, s.blocks, lds_bytes, stream, ka, qa);
+    };
+    return stripes ? with_radiance_instance<true>(mode, tris, launch) : with_radiance_instance<false>(mode, tris, launch);
 }
 
 // Step 4's tree over the partials of `points` points (stream-ordered after the path kernel).

@@ -15,12 +15,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "rt_abi.h"
 #include "rt_kernel_args.h"
+#include "rt_query_schedule.h"
 #include "rt_scene_math.h"
 #include "sphere_bvh.h"
 #include "tri_cone.h"
@@ -53,22 +55,25 @@ hipError_t rt_launch_brute_wf(const KernelArgs& ka, bool tris, bool scalar_strea
                               hipStream_t stream);
 size_t rt_brute_wf_tile_bytes(bool scalar_stream);
 uint32_t rt_brute_wf_chunk();
-uint32_t rt_query_threads(int mode);
+// the query kernels (query.hip, occlusion.hip, radiance.hip): per kernel the workgroup size of a
+// placement, the resident workgroups per CU, and the launch on a schedule of rt_query_schedule.h
+uint32_t rt_query_threads(int mode, bool tris);
 hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                            const void* rays, void* hits, uint64_t count, unsigned long long* counter,
-                           uint32_t wave_chunk, hipStream_t stream);
-uint32_t rt_occlusion_threads(int mode);
+                           hipStream_t stream);
+uint32_t rt_occlusion_threads(int mode, bool tris);
 hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
-                               uint32_t wave_chunk, uint32_t first_chunk, hipStream_t stream);
+                               hipStream_t stream);
 uint32_t rt_radiance_threads(int mode, bool tris);
-hipError_t rt_radiance_occupancy(int mode, bool tris, bool gather, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t blocks,
+hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                               const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
-                              unsigned long long* segments, uint32_t wave_chunk, uint32_t first_chunk,
-                              uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
+                              unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
+                              hipStream_t stream);
 hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
                                     hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
@@ -511,6 +516,37 @@ int hip_fail(rt_ctx* ctx, const char* what, hipError_t e) {
         hipError_t e_ = (call);                          \
         if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
     } while (0)
+
+// A caller's device pointer, as an entry point requires it.
+struct DevicePtr {
+    const void* p;
+    const char* name;
+    uintptr_t alignment;  // in bytes, a power of two
+    bool may_be_null;
+};
+
+// RT_OK when every pointer is device memory of the context's device at its alignment (or NULL
+// where that is allowed); else RT_E_INVALID with a message naming `entry` and the argument.
+int check_device_ptrs(rt_ctx* ctx, const char* entry, std::initializer_list<DevicePtr> ptrs) {
+    auto bad = [&](const DevicePtr& a, const std::string& why) {
+        return fail(ctx, RT_E_INVALID, std::string(entry) + ": " + a.name + " " + why);
+    };
+    for (const DevicePtr& a : ptrs) {
+        if (!a.p) {
+            if (a.may_be_null) continue;
+            return bad(a, "is NULL");
+        }
+        hipPointerAttribute_t attr{};
+        const hipError_t ea = hipPointerGetAttributes(&attr, a.p);
+        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return bad(a, "must be device memory of the context's device");
+        }
+        if ((uintptr_t)a.p & (a.alignment - 1u))
+            return bad(a, "must be " + std::to_string(a.alignment) + "-byte aligned");
+    }
+    return RT_OK;
+}
 
 void srgb_table(float out[256]) {
     // IEC 61966-2-1 decode of an 8-bit Rgba8UnormSrgb channel, rounded to f32.
@@ -1818,24 +1854,26 @@ int rt_synchronize(rt_ctx* ctx) {
     return RT_OK;
 }
 
+// rt_copy_{output,denoised,display}_to_device: the RGBA8 plane `src` into the caller's pitched
+// rows, stream-ordered. `missing`: why the entry point has no plane to copy (null: it has one).
+static int copy_plane_to_device(rt_ctx* ctx, const char* entry, const uint32_t* src, const char* missing,
+                                void* dst_device, uint32_t bytes_per_row) {
+    if (dst_device && missing) return fail(ctx, RT_E_INVALID, std::string(entry) + ": " + missing);
+    const int rc = check_device_ptrs(ctx, entry, {{dst_device, "dst_device", 1, false}});
+    if (rc) return rc;
+    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
+        return fail(ctx, RT_E_INVALID, std::string(entry) + ": bytes_per_row < 4 * width");
+    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, src, 4u * (size_t)ctx->width, 4u * (size_t)ctx->width,
+                                 ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
+    return RT_OK;
+}
+
 int rt_copy_output_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row) {
     RT_ENTER(ctx);  // queued frames launched first: the copy sees the last frame's output
-    if (!dst_device) return fail(ctx, RT_E_INVALID, "rt_copy_output_to_device: dst_device is NULL");
-    if (ctx->world > 1)  // a rank's output holds only its own tiles: gather first (rt_gather_frame)
-        return fail(ctx, RT_E_INVALID, "rt_copy_output_to_device: a rank context (world_size > 1) has no full frame");
-    {
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, dst_device);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID, "rt_copy_output_to_device: dst_device is not device memory of the context's device");
-        }
-    }
-    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
-        return fail(ctx, RT_E_INVALID, "rt_copy_output_to_device: bytes_per_row < 4 * width");
-    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_out, 4u * (size_t)ctx->width,
-                                 4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
+    // a rank's output holds only its own tiles: gather first (rt_gather_frame)
+    return copy_plane_to_device(ctx, "rt_copy_output_to_device", ctx->d_out,
+                                ctx->world > 1 ? "a rank context (world_size > 1) has no full frame" : nullptr,
+                                dst_device, bytes_per_row);
 }
 
 // ---- ray queries (query.hip) -------------------------------------------------------------------
@@ -1865,13 +1903,26 @@ static int query_enter(rt_ctx* ctx) {
 // its gather instance (points x samples).
 enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2, kQueryGather = 3 };
 
-static uint32_t query_threads(int kind, int mode, bool tris) {
-    return kind >= kQueryRadiance ? rt_radiance_threads(mode, tris)
-                                  : kind == kQueryAnyHit ? rt_occlusion_threads(mode) : rt_query_threads(mode);
-}
+// Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
+static const struct {
+    uint32_t (*threads)(int mode, bool tris);
+    hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+} kQueryKernels[4] = {{rt_query_threads, rt_query_occupancy},
+                      {rt_occlusion_threads, rt_occlusion_occupancy},
+                      {rt_radiance_threads, rt_radiance_occupancy},
+                      {rt_radiance_threads, rt_gather_occupancy}};
 
-static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, SceneLaunch& sl, size_t* lds_bytes,
-                       int* blocks_per_cu) {
+struct QueryLaunch {
+    KernelArgs ka{};
+    SceneLaunch sl;
+    size_t lds_bytes = 0;
+    uint32_t waves_per_block = 0;
+    uint64_t resident = 0;  // workgroups of the instance that the device holds at once
+};
+
+static int query_scene(rt_ctx* ctx, uint64_t count, int kind, QueryLaunch& q) {
+    KernelArgs& ka = q.ka;
+    SceneLaunch& sl = q.sl;
     scene_base_args(ctx, ka);
     ka.camera_rays = ctx->d_rays;
     int max_mode = ctx->force_global_scene ? 0 : ctx->max_lds_mode;
@@ -1886,21 +1937,18 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, Sc
         scene_carve(ctx, ka, max_mode, sl);
         const int rc = scene_accel_args(ctx, ka, sl);
         if (rc) return rc;
-        const uint32_t threads = query_threads(kind, sl.mode, sl.tris);
+        const uint32_t threads = kQueryKernels[kind].threads(sl.mode, sl.tris);
         ka.lds_leafbatch_offset = (uint32_t)al16(sl.lds_bytes);
-        *lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
+        q.lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
         if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_kind != kind ||
-            ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != *lds_bytes) {
+            ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != q.lds_bytes) {
             int n = 0;
-            const hipError_t e = kind >= kQueryRadiance
-                                     ? rt_radiance_occupancy(sl.mode, sl.tris, kind == kQueryGather, *lds_bytes, &n)
-                                 : kind == kQueryAnyHit ? rt_occlusion_occupancy(sl.mode, sl.tris, *lds_bytes, &n)
-                                                        : rt_query_occupancy(sl.mode, sl.tris, *lds_bytes, &n);
+            const hipError_t e = kQueryKernels[kind].occupancy(sl.mode, sl.tris, q.lds_bytes, &n);
             if (e != hipSuccess) (void)hipGetLastError();
             ctx->q_occ_mode = sl.mode;
             ctx->q_occ_kind = kind;
             ctx->q_occ_tris = sl.tris;
-            ctx->q_occ_lds = *lds_bytes;
+            ctx->q_occ_lds = q.lds_bytes;
             ctx->q_occ_blocks = e == hipSuccess ? n : 0;
         }
         if (ctx->q_occ_blocks > 0) break;
@@ -1908,7 +1956,8 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, Sc
         if (sl.mode == 0) return fail(ctx, RT_E_HIP, "ray query: the kernel does not fit the device");
         max_mode = sl.mode;
     }
-    *blocks_per_cu = ctx->q_occ_blocks;
+    q.waves_per_block = kQueryKernels[kind].threads(sl.mode, sl.tris) / 64u;
+    q.resident = (uint64_t)ctx->q_occ_blocks * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
     return RT_OK;
 }
 
@@ -1916,43 +1965,21 @@ static int query_scene(rt_ctx* ctx, KernelArgs& ka, uint64_t count, int kind, Sc
 // rt_hit records, or with `any_hit` one occlusion byte per rt_occlusion_ray.
 static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count, bool any_hit = false) {
     if (count == 0) return RT_OK;
-    KernelArgs ka{};
-    SceneLaunch sl;
-    size_t lds_bytes = 0;
-    int per_cu = 0;
-    const int rc = query_scene(ctx, ka, count, any_hit ? kQueryAnyHit : kQueryClosest, sl, &lds_bytes, &per_cu);
+    QueryLaunch q;
+    const int rc = query_scene(ctx, count, any_hit ? kQueryAnyHit : kQueryClosest, q);
     if (rc) return rc;
-    const uint32_t waves_per_block = (any_hit ? rt_occlusion_threads(sl.mode) : rt_query_threads(sl.mode)) / 64u;
-    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
-    const uint64_t wanted = (count + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
-    // rays per claim: about two claims per wave, whole waves of rays, at most 256
-    const uint64_t per_wave = count / ((uint64_t)blocks * waves_per_block * 2u);
-    const uint32_t wave_chunk = (uint32_t)std::min<uint64_t>(256u, std::max<uint64_t>(64u, (per_wave + 63u) & ~63ull));
+    // the closest-hit kernel takes every chunk from the counter; an any-hit wave owns its first
+    const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident,
+                                                     any_hit ? rtq::kNoChunkCap : 0u, rtq::kWalkChunkMax);
     RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
-    if (any_hit) {
-        // Each wave's own first chunk: whole waves of consecutive rays, about half the wave's share,
-        // taken without a claim (the resident waves' first claims would queue at one counter
-        // address, about 20 ns each, while nothing else runs). The counter deals the other half,
-        // which evens out what the first chunks cost. A batch of at most one wave of rays per wave
-        // claims nothing.
-        const uint64_t waves = (uint64_t)blocks * waves_per_block;
-        const uint32_t first_chunk = (uint32_t)std::max<uint64_t>(64u, (count / waves / 2u) & ~63ull);
-        const uint64_t rest = count > waves * first_chunk ? count - waves * first_chunk : 0;
-        const uint32_t rest_chunk =
-            (uint32_t)std::min<uint64_t>(256u, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
-        const hipError_t e = rt_launch_occlusion(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, hits, count,
-                                                 ctx->d_query_next, rest_chunk, first_chunk, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, "rt_occlusion_kernel launch", e);
-        return RT_OK;
-    }
-    const hipError_t e = rt_launch_query(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, hits, count, ctx->d_query_next,
-                                         wave_chunk, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, "rt_query_kernel launch", e);
+    const hipError_t e = (any_hit ? rt_launch_occlusion : rt_launch_query)(
+        q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, rays, hits, count, ctx->d_query_next, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, any_hit ? "rt_occlusion_kernel launch" : "rt_query_kernel launch", e);
     return RT_OK;
 }
 
-// The staging of rt_trace_rays and rt_pick: `n` rays then `n` records, on the device and pinned.
+// The staging of the host entry points and rt_pick: `n` rays then `n` records, on the device and
+// pinned.
 static int query_buffers(rt_ctx* ctx, size_t n) {
     if (ctx->query_buf_rays < n) {
         const int rc = grow_buffer(ctx, &ctx->d_query_buf, &ctx->query_buf_bytes, n * (sizeof(rt_query_ray) + sizeof(rt_hit)));
@@ -1969,22 +1996,50 @@ static int query_buffers(rt_ctx* ctx, size_t n) {
     return RT_OK;
 }
 
+// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather): the `count` records
+// of `in_bytes` each at host pointer `in` go through the pinned and the device scratch in chunks of
+// "query_chunk"; run(device in, device out, n) answers a chunk, and `out_bytes` per record come
+// back to `out`. Both scratch buffers hold the inputs at their base and the results at capacity x
+// 32 bytes (where the records of a closest-hit chunk go). With `count_segments` the context's
+// segment counter is zeroed first and read back after the last chunk, into the pinned bytes after
+// a chunk's results, for `segments` (which may be null).
+extern "C++" template <class Run>  // (a template inside the extern "C" block of the entry points)
+static int staged_query(rt_ctx* ctx, const void* in, size_t in_bytes, void* out, size_t out_bytes, uint64_t count,
+                        bool count_segments, uint64_t* segments, Run run) {
+    int rc = query_enter(ctx);
+    if (rc) return rc;
+    if (count_segments && !ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    unsigned char* d_in = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* d_out = d_in + ctx->query_buf_rays * sizeof(rt_query_ray);
+    unsigned char* h_in = static_cast<unsigned char*>(ctx->query_pinned);
+    unsigned char* h_out = h_in + ctx->query_pinned_rays * sizeof(rt_query_ray);
+    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_out + chunk * out_bytes);
+    if (count_segments)
+        RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_in, static_cast<const unsigned char*>(in) + done * in_bytes, n * in_bytes);
+        RT_HIP(ctx, hipMemcpyAsync(d_in, h_in, n * in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run(d_in, d_out, n))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_out, d_out, n * out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (count_segments && done + n == count)
+            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(static_cast<unsigned char*>(out) + done * out_bytes, h_out, n * out_bytes);
+        done += n;
+    }
+    if (count_segments && segments) *segments = *h_segs;
+    return RT_OK;
+}
+
 int rt_trace_rays_device(rt_ctx* ctx, const void* rays_device, void* hits_device, uint64_t count) {
     RT_ENTER_NOFLUSH(ctx);
     if (count == 0) return RT_OK;
-    if (!rays_device || !hits_device) return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays or hits is NULL");
-    for (const void* ptr : {rays_device, (const void*)hits_device}) {
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays and hits must be device memory of the context's device");
-        }
-    }
-    if (((uintptr_t)rays_device | (uintptr_t)hits_device) & 15u)
-        return fail(ctx, RT_E_INVALID, "rt_trace_rays_device: rays and hits must be 16-byte aligned");
-    const int rc = query_enter(ctx);
-    if (rc) return rc;
+    int rc = check_device_ptrs(ctx, "rt_trace_rays_device", {{rays_device, "rays", 16, false}, {hits_device, "hits", 16, false}});
+    if (rc || (rc = query_enter(ctx))) return rc;
     return run_query(ctx, rays_device, hits_device, count);
 }
 
@@ -1992,26 +2047,8 @@ int rt_trace_rays(rt_ctx* ctx, const rt_query_ray* rays, rt_hit* hits, uint64_t 
     RT_ENTER_NOFLUSH(ctx);
     if (count == 0) return RT_OK;
     if (!rays || !hits) return fail(ctx, RT_E_INVALID, "rt_trace_rays: rays or hits is NULL");
-    int rc = query_enter(ctx);
-    if (rc) return rc;
-    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
-    if ((rc = query_buffers(ctx, chunk))) return rc;
-    const size_t cap = ctx->query_buf_rays;
-    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
-    unsigned char* d_hits = d_rays + cap * sizeof(rt_query_ray);
-    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
-    unsigned char* h_hits = h_rays + ctx->query_pinned_rays * sizeof(rt_query_ray);
-    for (uint64_t done = 0; done < count;) {
-        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
-        std::memcpy(h_rays, rays + done, n * sizeof(rt_query_ray));
-        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_query_ray), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run_query(ctx, d_rays, d_hits, n))) return rc;
-        RT_HIP(ctx, hipMemcpyAsync(h_hits, d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(hits + done, h_hits, n * sizeof(rt_hit));
-        done += n;
-    }
-    return RT_OK;
+    return staged_query(ctx, rays, sizeof(rt_query_ray), hits, sizeof(rt_hit), count, false, nullptr,
+                        [&](const void* d_rays, void* d_hits, uint64_t n) { return run_query(ctx, d_rays, d_hits, n); });
 }
 
 int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit) {
@@ -2159,22 +2196,8 @@ int rt_read_denoised(rt_ctx* ctx, uint32_t* rgba8_out, float* rgba_f32_out) {
 
 int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row) {
     RT_ENTER_NOFLUSH(ctx);
-    if (!dst_device) return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: dst_device is NULL");
-    if (ctx->dn_result < 0) return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: no rt_denoise yet");
-    {
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, dst_device);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID,
-                        "rt_copy_denoised_to_device: dst_device is not device memory of the context's device");
-        }
-    }
-    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
-        return fail(ctx, RT_E_INVALID, "rt_copy_denoised_to_device: bytes_per_row < 4 * width");
-    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_dn_out, 4u * (size_t)ctx->width,
-                                 4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
+    return copy_plane_to_device(ctx, "rt_copy_denoised_to_device", ctx->d_dn_out,
+                                ctx->dn_result < 0 ? "no rt_denoise yet" : nullptr, dst_device, bytes_per_row);
 }
 
 // ---- temporal reprojection (denoise.hip) --------------------------------------------------------
@@ -2346,15 +2369,8 @@ int rt_display(rt_ctx* ctx, const rt_display_params* params, const void* plane_d
         if (ctx->dn_result < 0) return fail(ctx, RT_E_INVALID, "rt_display: no rt_denoise or rt_denoise_temporal yet");
         src = ctx->d_dn[ctx->dn_result];
     } else {
-        if (!plane_device) return fail(ctx, RT_E_INVALID, "rt_display: plane_device is NULL");
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, plane_device);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID, "rt_display: plane_device must be device memory of the context's device");
-        }
-        if ((uintptr_t)plane_device & 15u)
-            return fail(ctx, RT_E_INVALID, "rt_display: plane_device must be 16-byte aligned");
+        const int rcp = check_device_ptrs(ctx, "rt_display", {{plane_device, "plane_device", 16, false}});
+        if (rcp) return rcp;
         src = static_cast<const float4*>(plane_device);
     }
     int rc;
@@ -2387,22 +2403,8 @@ int rt_read_display(rt_ctx* ctx, uint32_t* rgba8_out) {
 
 int rt_copy_display_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row) {
     RT_ENTER_NOFLUSH(ctx);
-    if (!dst_device) return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: dst_device is NULL");
-    if (!ctx->disp_valid) return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: no rt_display yet");
-    {
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, dst_device);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID,
-                        "rt_copy_display_to_device: dst_device is not device memory of the context's device");
-        }
-    }
-    if ((uint64_t)bytes_per_row < 4ull * ctx->width)
-        return fail(ctx, RT_E_INVALID, "rt_copy_display_to_device: bytes_per_row < 4 * width");
-    RT_HIP(ctx, hipMemcpy2DAsync(dst_device, bytes_per_row, ctx->d_disp_out, 4u * (size_t)ctx->width,
-                                 4u * (size_t)ctx->width, ctx->height, hipMemcpyDeviceToDevice, ctx->stream));
-    return RT_OK;
+    return copy_plane_to_device(ctx, "rt_copy_display_to_device", ctx->d_disp_out,
+                                ctx->disp_valid ? nullptr : "no rt_display yet", dst_device, bytes_per_row);
 }
 
 int rt_display_state(rt_ctx* ctx, float* exposure, uint32_t* histogram, uint64_t* metered) {
@@ -2436,20 +2438,9 @@ int rt_display_reset(rt_ctx* ctx) {
 int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count) {
     RT_ENTER_NOFLUSH(ctx);
     if (count == 0) return RT_OK;
-    if (!rays_device || !occluded_device)
-        return fail(ctx, RT_E_INVALID, "rt_occluded_device: rays or occluded is NULL");
-    for (const void* ptr : {rays_device, (const void*)occluded_device}) {
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID,
-                        "rt_occluded_device: rays and occluded must be device memory of the context's device");
-        }
-    }
-    if ((uintptr_t)rays_device & 15u) return fail(ctx, RT_E_INVALID, "rt_occluded_device: rays must be 16-byte aligned");
-    const int rc = query_enter(ctx);
-    if (rc) return rc;
+    int rc = check_device_ptrs(ctx, "rt_occluded_device",
+                               {{rays_device, "rays", 16, false}, {occluded_device, "occluded", 1, false}});
+    if (rc || (rc = query_enter(ctx))) return rc;
     return run_query(ctx, rays_device, occluded_device, count, true);
 }
 
@@ -2457,25 +2448,8 @@ int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, ui
     RT_ENTER_NOFLUSH(ctx);
     if (count == 0) return RT_OK;
     if (!rays || !occluded) return fail(ctx, RT_E_INVALID, "rt_occluded: rays or occluded is NULL");
-    int rc = query_enter(ctx);
-    if (rc) return rc;
-    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
-    if ((rc = query_buffers(ctx, chunk))) return rc;
-    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
-    unsigned char* d_occ = d_rays + ctx->query_buf_rays * sizeof(rt_occlusion_ray);
-    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
-    unsigned char* h_occ = h_rays + ctx->query_pinned_rays * sizeof(rt_occlusion_ray);
-    for (uint64_t done = 0; done < count;) {
-        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
-        std::memcpy(h_rays, rays + done, n * sizeof(rt_occlusion_ray));
-        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_occlusion_ray), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run_query(ctx, d_rays, d_occ, n, true))) return rc;
-        RT_HIP(ctx, hipMemcpyAsync(h_occ, d_occ, n, hipMemcpyDeviceToHost, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(occluded + done, h_occ, n);
-        done += n;
-    }
-    return RT_OK;
+    return staged_query(ctx, rays, sizeof(rt_occlusion_ray), occluded, 1, count, false, nullptr,
+                        [&](const void* d_rays, void* d_occ, uint64_t n) { return run_query(ctx, d_rays, d_occ, n, true); });
 }
 
 // ---- radiance queries (radiance.hip) -----------------------------------------------------------
@@ -2484,16 +2458,24 @@ int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, ui
 // calls above. rt_radiance stages through the same buffers (32 B in, 16 B out per ray: the sums go
 // where the records of a closest-hit chunk would).
 
-// Rays per chunk of a radiance launch (whole waves of rays): the cap of a wave's own first chunk
-// and of the chunks the counter deals (DESIGN.md §5.4e has the measurement behind the values).
-#ifndef RT_RADIANCE_FIRST_CHUNK_MAX
-#define RT_RADIANCE_FIRST_CHUNK_MAX 128u
-#endif
-#ifndef RT_RADIANCE_CHUNK_MAX
-#define RT_RADIANCE_CHUNK_MAX 128u
-#endif
-constexpr uint64_t kRadianceFirstChunkMax = RT_RADIANCE_FIRST_CHUNK_MAX;
-constexpr uint64_t kRadianceChunkMax = RT_RADIANCE_CHUNK_MAX;
+// The head of a radiance or gather launch (`kind`) of `count` records into `radiance`: zero bounces
+// are answered here (*answered), else `q` receives the scene view and the shading arguments.
+static int path_query_scene(rt_ctx* ctx, void* radiance, uint64_t count, uint32_t bounces, uint32_t samples, int kind,
+                            QueryLaunch& q, bool* answered) {
+    *answered = bounces == 0;
+    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
+        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
+        return RT_OK;
+    }
+    // the placement threshold of the other queries, on the walks the call runs at least
+    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
+    const int rc = query_scene(ctx, walks, kind, q);
+    if (rc) return rc;
+    q.ka.bounces = bounces;
+    q.ka.drain_threshold = ctx->drain_threshold;
+    q.ka.drain_min_steps = ctx->drain_min_steps;
+    return RT_OK;
+}
 
 // Path-traces `count` rays at device pointer `rays` into `radiance`, stream-ordered on the primary
 // stream; the batch's counted segments are added to the device counter `segments` (null: not
@@ -2501,39 +2483,15 @@ constexpr uint64_t kRadianceChunkMax = RT_RADIANCE_CHUNK_MAX;
 static int run_radiance(rt_ctx* ctx, const void* rays, void* radiance, uint64_t count, uint32_t bounces,
                         uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
     if (count == 0) return RT_OK;
-    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
-        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
-        return RT_OK;
-    }
-    KernelArgs ka{};
-    SceneLaunch sl;
-    size_t lds_bytes = 0;
-    int per_cu = 0;
-    // the placement threshold of the other queries, on the walks the batch runs at least
-    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
-    const int rc = query_scene(ctx, ka, walks, kQueryRadiance, sl, &lds_bytes, &per_cu);
-    if (rc) return rc;
-    ka.bounces = bounces;
-    ka.drain_threshold = ctx->drain_threshold;
-    ka.drain_min_steps = ctx->drain_min_steps;
-    const uint32_t waves_per_block = rt_radiance_threads(sl.mode, sl.tris) / 64u;
-    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
-    const uint64_t wanted = (count + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
-    // run_query's schedule for the occlusion kernel -- each wave's own first chunk (whole waves of
-    // rays, no claim), the counter deals the rest -- in chunks of at most 128 rays: a ray here is
-    // a whole path, so a chunk of consecutive rays is uniformly dear or cheap and larger chunks
-    // end the launch on the waves that drew the dear ones
-    const uint64_t waves = (uint64_t)blocks * waves_per_block;
-    const uint32_t first_chunk = (uint32_t)std::min<uint64_t>(
-        kRadianceFirstChunkMax, std::max<uint64_t>(64u, (count / waves / 2u) & ~63ull));
-    const uint64_t rest = count > waves * first_chunk ? count - waves * first_chunk : 0;
-    const uint32_t rest_chunk = (uint32_t)std::min<uint64_t>(
-        kRadianceChunkMax, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
+    QueryLaunch q;
+    bool answered;
+    const int rc = path_query_scene(ctx, radiance, count, bounces, samples, kQueryRadiance, q, &answered);
+    if (rc || answered) return rc;
+    const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident, rtq::kRadianceFirstChunkMax,
+                                                     rtq::kRadianceChunkMax);
     RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
-    const hipError_t e = rt_launch_radiance(ka, sl.mode, sl.tris, lds_bytes, blocks, rays, radiance, count,
-                                            ctx->d_query_next, segments, rest_chunk, first_chunk, first_sample,
-                                            samples, 0u, ctx->stream);
+    const hipError_t e = rt_launch_radiance(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, rays, radiance, count,
+                                            ctx->d_query_next, segments, first_sample, samples, 0u, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel launch", e);
     return RT_OK;
 }
@@ -2543,24 +2501,10 @@ int rt_radiance_device(rt_ctx* ctx, const void* rays_device, void* radiance_devi
     RT_ENTER_NOFLUSH(ctx);
     if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_radiance_device: samples is 0");
     if (count == 0) return RT_OK;
-    if (!rays_device || !radiance_device)
-        return fail(ctx, RT_E_INVALID, "rt_radiance_device: rays or radiance is NULL");
-    for (const void* ptr : {rays_device, (const void*)radiance_device, (const void*)segments_device}) {
-        if (!ptr) continue;  // (segments may be NULL)
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID,
-                        "rt_radiance_device: rays, radiance and segments must be device memory of the context's device");
-        }
-    }
-    if (((uintptr_t)rays_device | (uintptr_t)radiance_device) & 15u)
-        return fail(ctx, RT_E_INVALID, "rt_radiance_device: rays and radiance must be 16-byte aligned");
-    if ((uintptr_t)segments_device & 7u)
-        return fail(ctx, RT_E_INVALID, "rt_radiance_device: segments must be 8-byte aligned");
-    const int rc = query_enter(ctx);
-    if (rc) return rc;
+    int rc = check_device_ptrs(ctx, "rt_radiance_device", {{rays_device, "rays", 16, false},
+                                                           {radiance_device, "radiance", 16, false},
+                                                           {segments_device, "segments", 8, true}});
+    if (rc || (rc = query_enter(ctx))) return rc;
     return run_radiance(ctx, rays_device, radiance_device, count, bounces, first_sample, samples,
                         static_cast<unsigned long long*>(segments_device));
 }
@@ -2574,34 +2518,10 @@ int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint6
         return RT_OK;
     }
     if (!rays || !radiance) return fail(ctx, RT_E_INVALID, "rt_radiance: rays or radiance is NULL");
-    int rc = query_enter(ctx);
-    if (rc) return rc;
-    if (!ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
-    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
-    if ((rc = query_buffers(ctx, chunk))) return rc;
-    unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_query_buf);
-    unsigned char* d_rad = d_rays + ctx->query_buf_rays * sizeof(rt_radiance_ray);
-    unsigned char* h_rays = static_cast<unsigned char*>(ctx->query_pinned);
-    unsigned char* h_rad = h_rays + ctx->query_pinned_rays * sizeof(rt_radiance_ray);
-    // the counter's readback lands in the pinned buffer after the chunk's sums (16 of the 64
-    // bytes per ray a closest-hit record would take)
-    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_rad + chunk * 16u);
-    RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
-    for (uint64_t done = 0; done < count;) {
-        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
-        std::memcpy(h_rays, rays + done, n * sizeof(rt_radiance_ray));
-        RT_HIP(ctx, hipMemcpyAsync(d_rays, h_rays, n * sizeof(rt_radiance_ray), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run_radiance(ctx, d_rays, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs))) return rc;
-        RT_HIP(ctx, hipMemcpyAsync(h_rad, d_rad, n * 16u, hipMemcpyDeviceToHost, ctx->stream));
-        done += n;
-        if (done == count)
-            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(radiance + 4u * (done - n), h_rad, n * 16u);
-    }
-    if (segments) *segments = *h_segs;
-    return RT_OK;
+    return staged_query(ctx, rays, sizeof(rt_radiance_ray), radiance, 16, count, true, segments,
+                        [&](const void* d_rays, void* d_rad, uint64_t n) {
+                            return run_radiance(ctx, d_rays, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs);
+                        });
 }
 
 // ---- gather queries (radiance.hip, kGather) -----------------------------------------------------
@@ -2616,44 +2536,24 @@ int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint6
 static int run_gather(rt_ctx* ctx, const void* points, void* radiance, uint64_t count, uint32_t bounces,
                       uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
     if (count == 0) return RT_OK;
-    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
-        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
-        return RT_OK;
-    }
-    KernelArgs ka{};
-    SceneLaunch sl;
-    size_t lds_bytes = 0;
-    int per_cu = 0;
-    // the placement threshold of the other queries, on the walks the call runs at least
-    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
-    int rc = query_scene(ctx, ka, walks, kQueryGather, sl, &lds_bytes, &per_cu);
-    if (rc) return rc;
-    ka.bounces = bounces;
-    ka.drain_threshold = ctx->drain_threshold;
-    ka.drain_min_steps = ctx->drain_min_steps;
+    QueryLaunch q;
+    bool answered;
+    int rc = path_query_scene(ctx, radiance, count, bounces, samples, kQueryGather, q, &answered);
+    if (rc || answered) return rc;
     const uint32_t stripes = std::min<uint32_t>(samples, 64u);
     const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
     if ((rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u))) return rc;
-    const uint32_t waves_per_block = rt_radiance_threads(sl.mode, sl.tris) / 64u;
-    const uint64_t resident = (uint64_t)per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
     for (uint64_t done = 0; done < count;) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
         // the launch is sized by its items, (point, stripe) pairs: at most 2^20 x 64
         const uint64_t items = (uint64_t)n * stripes;
-        const uint64_t wanted = (items + 64ull * waves_per_block - 1) / (64ull * waves_per_block);
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>(wanted, resident);
-        // run_radiance's schedule, over items
-        const uint64_t waves = (uint64_t)blocks * waves_per_block;
-        const uint32_t first_chunk = (uint32_t)std::min<uint64_t>(
-            kRadianceFirstChunkMax, std::max<uint64_t>(64u, (items / waves / 2u) & ~63ull));
-        const uint64_t rest = items > waves * first_chunk ? items - waves * first_chunk : 0;
-        const uint32_t rest_chunk = (uint32_t)std::min<uint64_t>(
-            kRadianceChunkMax, std::max<uint64_t>(64u, (rest / (waves * 2u) + 63u) & ~63ull));
+        const rtq::QuerySchedule s = rtq::query_schedule(items, q.waves_per_block, q.resident,
+                                                         rtq::kRadianceFirstChunkMax, rtq::kRadianceChunkMax);
         RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
-        hipError_t e = rt_launch_radiance(ka, sl.mode, sl.tris, lds_bytes, blocks,
+        hipError_t e = rt_launch_radiance(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s,
                                           static_cast<const unsigned char*>(points) + done * sizeof(rt_gather_point),
-                                          ctx->d_gather_partials, items, ctx->d_query_next, segments, rest_chunk,
-                                          first_chunk, first_sample, samples, stripes, ctx->stream);
+                                          ctx->d_gather_partials, items, ctx->d_query_next, segments, first_sample,
+                                          samples, stripes, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel (gather) launch", e);
         e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(radiance) + done * 16u, n,
                                      stripes, ctx->stream);
@@ -2668,24 +2568,10 @@ int rt_gather_device(rt_ctx* ctx, const void* points_device, void* radiance_devi
     RT_ENTER_NOFLUSH(ctx);
     if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_gather_device: samples is 0");
     if (count == 0) return RT_OK;
-    if (!points_device || !radiance_device)
-        return fail(ctx, RT_E_INVALID, "rt_gather_device: points or radiance is NULL");
-    for (const void* ptr : {points_device, (const void*)radiance_device, (const void*)segments_device}) {
-        if (!ptr) continue;  // (segments may be NULL)
-        hipPointerAttribute_t attr{};
-        const hipError_t ea = hipPointerGetAttributes(&attr, ptr);
-        if (ea != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_E_INVALID,
-                        "rt_gather_device: points, radiance and segments must be device memory of the context's device");
-        }
-    }
-    if (((uintptr_t)points_device | (uintptr_t)radiance_device) & 15u)
-        return fail(ctx, RT_E_INVALID, "rt_gather_device: points and radiance must be 16-byte aligned");
-    if ((uintptr_t)segments_device & 7u)
-        return fail(ctx, RT_E_INVALID, "rt_gather_device: segments must be 8-byte aligned");
-    const int rc = query_enter(ctx);
-    if (rc) return rc;
+    int rc = check_device_ptrs(ctx, "rt_gather_device", {{points_device, "points", 16, false},
+                                                         {radiance_device, "radiance", 16, false},
+                                                         {segments_device, "segments", 8, true}});
+    if (rc || (rc = query_enter(ctx))) return rc;
     return run_gather(ctx, points_device, radiance_device, count, bounces, first_sample, samples,
                       static_cast<unsigned long long*>(segments_device));
 }
@@ -2699,33 +2585,10 @@ int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance, uint6
         return RT_OK;
     }
     if (!points || !radiance) return fail(ctx, RT_E_INVALID, "rt_gather: points or radiance is NULL");
-    int rc = query_enter(ctx);
-    if (rc) return rc;
-    if (!ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
-    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
-    if ((rc = query_buffers(ctx, chunk))) return rc;
-    // rt_radiance's staging: the points where its rays go, the results where its sums go
-    unsigned char* d_pts = static_cast<unsigned char*>(ctx->d_query_buf);
-    unsigned char* d_rad = d_pts + ctx->query_buf_rays * sizeof(rt_gather_point);
-    unsigned char* h_pts = static_cast<unsigned char*>(ctx->query_pinned);
-    unsigned char* h_rad = h_pts + ctx->query_pinned_rays * sizeof(rt_gather_point);
-    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_rad + chunk * 16u);
-    RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
-    for (uint64_t done = 0; done < count;) {
-        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
-        std::memcpy(h_pts, points + done, n * sizeof(rt_gather_point));
-        RT_HIP(ctx, hipMemcpyAsync(d_pts, h_pts, n * sizeof(rt_gather_point), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run_gather(ctx, d_pts, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs))) return rc;
-        RT_HIP(ctx, hipMemcpyAsync(h_rad, d_rad, n * 16u, hipMemcpyDeviceToHost, ctx->stream));
-        done += n;
-        if (done == count)
-            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::memcpy(radiance + 4u * (done - n), h_rad, n * 16u);
-    }
-    if (segments) *segments = *h_segs;
-    return RT_OK;
+    return staged_query(ctx, points, sizeof(rt_gather_point), radiance, 16, count, true, segments,
+                        [&](const void* d_pts, void* d_rad, uint64_t n) {
+                            return run_gather(ctx, d_pts, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs);
+                        });
 }
 
 int rt_read_output(rt_ctx* ctx, uint32_t* out) {
