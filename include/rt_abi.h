@@ -1069,7 +1069,8 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   0|256|512|1024 (0: by occupancy), "waves_per_cu" 0..32 (0: 16), "trav_threshold" 0..63
  *   (0: by scene), "drain_threshold" 0..63 (32), "drain_min_steps" (64), "leaf_batch" 0..8
  *   (0: by scene), "queue_stripes" 1..64 (32), "tile_schedule" 1|0, "frame_parallel" 1|0,
- *   "batch_overlap" 1|0, "batch_schedule" 0|1, "unit_tile_major" 1|0, "batch_memory_mb"
+ *   "batch_overlap" 1|0, "batch_schedule" 0|1, "unit_tile_major" 1|0, "frame_par_instance" 1|0
+ *   (0: frame-parallel batches run the generic instance of the path kernel), "batch_memory_mb"
  *   (an eighth of device memory), "sphere_bvh" 1|0, "sphere_leaf" 0..64 (0: default),
  *   "sphere_octants" 1|0, "sphere_box_order" 1|0, "tri_bvh" 1|0 (0: the reference's sweep),
  *   "tri_octants" 1|0, "tri_qnodes" 1|0, "coop_leaves" 1|0, "stage_subs" 1|0,
@@ -1162,12 +1163,16 @@ RT_API int rt_launch_config(rt_ctx* ctx, uint32_t* threads, uint32_t* blocks, ui
  * the path kernel, the coherent primary-ray pre-pass, the batch resolve pass, or the
  * brute-force sweep kernel instead of the path kernel (with RT_PASS_BRUTE_STREAM, ABI 12:
  * its scalar-cache variant, rt_set_brute_force mode 2). Bit 32 (RT_PASS_TREELET, an ABI-12
- * treelet wavefront measured 2.9x slower than the path kernel on C5 and removed) is not set. */
+ * treelet wavefront measured 2.9x slower than the path kernel on C5 and removed) is not set.
+ * RT_PASS_PATH_FRAME_PAR (with RT_PASS_PATH): the path kernel ran as its frame-parallel
+ * instance -- a frame-parallel batch with bounces >= 1, unless the tuning key
+ * "frame_par_instance" is 0 -- and not as the generic instance that serves every launch. */
 #define RT_PASS_PATH 1u
 #define RT_PASS_PRIMARY 2u
 #define RT_PASS_RESOLVE 4u
 #define RT_PASS_BRUTE 8u
 #define RT_PASS_BRUTE_STREAM 16u
+#define RT_PASS_PATH_FRAME_PAR 64u
 RT_API int rt_last_launch_passes(rt_ctx* ctx, uint32_t* passes);
 
 /* Diagnostic counters (filled only by builds compiled with -DRT_DIAG or

@@ -41,6 +41,26 @@
 
 using namespace rtk;
 
+// Launch constants read where they are used (the frame-parallel instance of the path kernel): a
+// field of the kernel's KernelArgs loaded from the kernel-argument segment (scalar loads through
+// the scalar cache). `kp` is made opaque once per pass of the outer loop (kernarg_fresh), so the
+// loads are issued at the use and their results are not kept live, and spilled, across the loop.
+typedef const __attribute__((address_space(4))) unsigned char* KernargPtr;
+__device__ __forceinline__ KernargPtr kernarg_fresh(KernargPtr kp) {
+    asm volatile("" : "+s"(kp));
+    return kp;
+}
+#define RT_KERNARG(kp, field)                                                                        \
+    (*reinterpret_cast<const __attribute__((address_space(4))) decltype(KernelArgs::field)*>(        \
+        (kp) + __builtin_offsetof(KernelArgs, field)))
+__device__ __forceinline__ ShadeArgs load_shade_args(KernargPtr kp) {
+    return ShadeArgs{RT_KERNARG(kp, textures),        RT_KERNARG(kp, env),           RT_KERNARG(kp, texture_width),
+                     RT_KERNARG(kp, texture_height),  RT_KERNARG(kp, env_map_width), RT_KERNARG(kp, env_map_height),
+                     RT_KERNARG(kp, material_count),  RT_KERNARG(kp, tex_w),         RT_KERNARG(kp, tex_h),
+                     RT_KERNARG(kp, tex_layers),      RT_KERNARG(kp, env_w),         RT_KERNARG(kp, env_h),
+                     RT_KERNARG(kp, env_uniform),     RT_KERNARG(kp, bounces)};
+}
+
 constexpr uint32_t kPrimaryThreads = 1024;  // default: 16 units per workgroup, sharing one LDS image of the scene
 
 // The tile queue, striped over the XCDs. One device-scope atomic counter on a
@@ -110,11 +130,13 @@ __device__ __forceinline__ uint32_t claim_tile(const KernelArgs& ka, TileQueue& 
 // frame-parallel batch, the frame: frame-major positions (a cost-ordered launch
 // then ends on the last frame's cheapest tiles) or tile-major (a tile's frames
 // are claimed one after another: the same camera rays, near-identical primary
-// walks). 0xffffffff (empty queue) stays so.
+// walks). 0xffffffff (empty queue) stays so. kFramePar: the launch is known to be
+// a frame-parallel batch (the frame-parallel instance of the path kernel).
+template <bool kFramePar>
 __device__ __forceinline__ uint32_t unit_tile(const KernelArgs& ka, uint32_t pos, uint32_t& frame) {
     if (pos == 0xffffffffu) return pos;
     uint32_t q;
-    if (!ka.frame_light) {
+    if (!kFramePar && !ka.frame_light) {
         frame = 0u;
         q = pos;
     } else if (ka.unit_tile_major) {
@@ -294,12 +316,21 @@ struct WalkStepCount {
 // wave never idles behind one long path while work remains. A pixel's samples
 // (compute_per_frame) run back to back on one lane, so the accumulation is
 // summed in the reference's order (:160-163) and results are bit-identical.
-template <int kMode, uint32_t kThreads, bool kTris>
+//
+// kFramePar selects the frame-parallel instance ("Frame-parallel instance"): the launch is a
+// frame-parallel batch (ka.frame_light set, accumulating) with bounces >= 1, which
+// the host guarantees (rt_path_frame_par_instance, rt_abi.cpp). A finished sample
+// then only stores its light, so the instance holds no in-lane accumulation
+// (`pix`), no store_frame, no in-lane frame advance, no run-time test of the launch
+// mode, and no sample that ends without a trace in setup. The generic instance
+// (kFramePar false) serves every launch mode, frame-parallel batches included.
+template <int kMode, uint32_t kThreads, bool kTris, bool kFramePar>
 __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ uint32_t block_rays;
 
     const uint32_t tid = threadIdx.x;
+    const KernargPtr kernarg = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
     if (ka.launch_clock && tid == 0) atomicMax(ka.launch_clock, ~(unsigned long long)wall_clock64());
     float* l_srgb = reinterpret_cast<float*>(lds + ka.lds_srgb_offset);
     SceneView sv{ka.sphere_slots, ka.sphere_orig, ka.sphere_material, ka.sphere_bvh, ka.materials, nullptr,
@@ -380,7 +411,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
     if (tid == 0) l_cam[32] = ka.aspect;
     __syncthreads();
 
-    const bool accumulate = ka.accumulate == 1u;
+    const bool accumulate = kFramePar || ka.accumulate == 1u;
     const uint32_t samples = accumulate ? ka.compute_per_frame : 1u;  // :158-175
 
     // Lane states. A lane owns one pixel at a time and one ray of its path.
@@ -388,7 +419,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
     uint32_t rays = 0;
     uint32_t lane_tile = 0;  // local tile of the lane's pixel (tile costs)
     uint32_t lane_slot = 0;  // the pixel's slot in its tile (frame-parallel light stores)
-    const bool frame_par = ka.frame_light != nullptr;
+    const bool frame_par = kFramePar || ka.frame_light != nullptr;
     uint32_t mode = kIdle;
     uint32_t index = 0, sample = 0, frame = 0;
     float4 pix = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -444,43 +475,50 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
         if (accumulate) ka.accum[index] = pix;      // :164
         ka.output[index] = pack_rgba8(r, g, b, a);  // :178
     };
+    // frame-parallel batch: this sample's light, added to the accumulation in order
+    // by rt_resolve_frames_kernel; then the pixel's next sample, or idle
+    auto finish_sample_frame_par = [&]() {
+        const size_t plane = kFramePar ? (size_t)ka.light_plane : (size_t)ka.owned_tiles * 64u;
+        const size_t slot = (size_t)(frame * samples + sample) * plane + (size_t)lane_tile * 64u + lane_slot;
+        ka.frame_light[slot] = make_float4(p.light.x, p.light.y, p.light.z, p.light.w);
+        sample += 1;
+        if (sample < samples) {
+            start_sample(ka, index, random_index(), pixel_ray(ka, l_cam, index, index % ka.width, index / ka.width), p);
+            mode = primary_start();
+        } else {
+            mode = kIdle;
+        }
+    };
     auto finish_sample = [&]() {
-        if (frame_par) {
-            // frame-parallel batch: this sample's light, added to the
-            // accumulation in order by rt_resolve_frames_kernel
-            const size_t slot = (size_t)(frame * samples + sample) * ((size_t)ka.owned_tiles * 64u) +
-                                (size_t)lane_tile * 64u + lane_slot;
-            ka.frame_light[slot] = make_float4(p.light.x, p.light.y, p.light.z, p.light.w);
+        if constexpr (kFramePar) {
+            finish_sample_frame_par();
+        } else {
+            if (frame_par) {
+                finish_sample_frame_par();
+                return;
+            }
             sample += 1;
+            if (accumulate) {
+                pix.x = pix.x + p.light.x;
+                pix.y = pix.y + p.light.y;
+                pix.z = pix.z + p.light.z;
+                pix.w = pix.w + p.light.w;
+            }
+            if (sample == samples && frame + 1u < ka.frames) {
+                // a multi-frame launch: every frame writes its result, exactly as
+                // the sequence of single-frame dispatches it stands for would
+                store_frame();
+                frame += 1;
+                sample = 0;
+            }
             if (sample < samples) {
                 start_sample(ka, index, random_index(), pixel_ray(ka, l_cam, index, index % ka.width, index / ka.width),
                              p);
                 mode = primary_start();
             } else {
+                store_frame();
                 mode = kIdle;
             }
-            return;
-        }
-        sample += 1;
-        if (accumulate) {
-            pix.x = pix.x + p.light.x;
-            pix.y = pix.y + p.light.y;
-            pix.z = pix.z + p.light.z;
-            pix.w = pix.w + p.light.w;
-        }
-        if (sample == samples && frame + 1u < ka.frames) {
-            // a multi-frame launch: every frame writes its result, exactly as
-            // the sequence of single-frame dispatches it stands for would
-            store_frame();
-            frame += 1;
-            sample = 0;
-        }
-        if (sample < samples) {
-            start_sample(ka, index, random_index(), pixel_ray(ka, l_cam, index, index % ka.width, index / ka.width), p);
-            mode = primary_start();
-        } else {
-            store_frame();
-            mode = kIdle;
         }
     };
 
@@ -493,7 +531,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
     // blockIdx / 8 spreads an XCD's blocks over its stripes when there are more)
     TileQueue queue{(xcc_id() + 8u * (blockIdx.x >> 3)) % ka.queue_stripes, 0u};
     uint32_t tile_frame = 0;         // frame of the claimed unit (frame-parallel batches), wave-uniform
-    uint32_t tile = unit_tile(ka, claim_tile(ka, queue), tile_frame);  // wave-uniform
+    uint32_t tile = unit_tile<kFramePar>(ka, claim_tile(ka, queue), tile_frame);  // wave-uniform
     uint32_t next = 0;               // next pixel slot of `tile`, wave-uniform
 #ifdef RT_DIAG
     unsigned long long iters = 0, trav_cyc = 0, steps = 0, step_lanes = 0, shade_cyc = 0, refill_cyc = 0,
@@ -541,10 +579,20 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 #endif
             ++rays;
             RT_ISA_MARK("shade");
-            if (shade<(kMode >= 1)>(sv, ka, p, h)) {
+            bool ended;
+            uint32_t bounce_limit;
+            if constexpr (kFramePar) {
+                const ShadeArgs sa = load_shade_args(kernarg_fresh(kernarg));
+                ended = shade<(kMode >= 1)>(sv, sa, p, h);
+                bounce_limit = sa.bounces;
+            } else {
+                ended = shade<(kMode >= 1)>(sv, ka, p, h);
+                bounce_limit = ka.bounces;
+            }
+            if (ended) {
                 // rays of the sample: one per bounce, plus the escaping one unless the limit ended it
                 fin = true;
-                fin_rays = p.bounce + (p.bounce < ka.bounces ? 1u : 0u);
+                fin_rays = p.bounce + (p.bounce < bounce_limit ? 1u : 0u);
                 finish_sample();
             } else {
                 mode = kSetup;
@@ -577,7 +625,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                         sample = 0;
                         frame = tile_frame;
                         mode = kSetup;
-                        if (accumulate && !frame_par) pix = ka.accum[index];  // :156
+                        if (!kFramePar && accumulate && !frame_par) pix = ka.accum[index];  // :156
                         start_sample(ka, index, random_index(), pixel_ray(ka, l_cam, index, x, y), p);
                         mode = primary_start();
                     }
@@ -585,7 +633,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
             }
             next += min((uint32_t)__popcll(need), avail);
             if (next == 64u) {
-                tile = unit_tile(ka, claim_tile(ka, queue), tile_frame);
+                tile = unit_tile<kFramePar>(ka, claim_tile(ka, queue), tile_frame);
                 next = 0;
             #ifdef RT_DIAG_TAIL
                 if (tile >= ka.owned_tiles && wave_dry == 0) wave_dry = realtime();
@@ -609,8 +657,10 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 #endif
         RT_ISA_MARK("setup");
         if (mode == kSetup) {
-            while (mode == kSetup && p.bounce >= ka.bounces) finish_sample();
-            if (mode == kSetup) {
+            // (the frame-parallel instance runs with bounces >= 1: every sample starts with a trace)
+            if constexpr (!kFramePar)
+                while (mode == kSetup && p.bounce >= ka.bounces) finish_sample();
+            if (kFramePar || mode == kSetup) {
                 trace_begin<kTris>(sv, ka, p.o, p.d, ts);
                 mode = ts.phase == 2 ? kDone : kTrav;
             }
@@ -856,11 +906,15 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 // the size with the most resident waves up to a cap (rt_pathtrace_pick_config).
 // Sphere-only scenes get kernels without the triangle side (fewer live scalar
 // registers: the kernel arguments of the triangle path no longer spill).
-// (mode, threads, triangles)
-#define RT_FOR_EACH_CONFIG(X)                                                                                   \
-    X(0, 256, true) X(0, 512, true) X(0, 1024, true) X(1, 256, true) X(1, 512, true) X(1, 1024, true)          \
-    X(2, 256, true) X(2, 512, true) X(2, 1024, true) X(0, 256, false) X(0, 512, false) X(0, 1024, false)       \
-    X(1, 256, false) X(1, 512, false) X(1, 1024, false)
+// Each comes twice: the generic instance, which serves every launch mode, and the
+// frame-parallel instance (kFramePar), which the host selects for frame-parallel
+// batches with bounces >= 1 (rt_path_frame_par_instance, rt_abi.cpp).
+// (mode, threads, triangles, frame-parallel instance)
+#define RT_FOR_EACH_SHAPE(X, FP)                                                                                \
+    X(0, 256, true, FP) X(0, 512, true, FP) X(0, 1024, true, FP) X(1, 256, true, FP) X(1, 512, true, FP)       \
+    X(1, 1024, true, FP) X(2, 256, true, FP) X(2, 512, true, FP) X(2, 1024, true, FP) X(0, 256, false, FP)     \
+    X(0, 512, false, FP) X(0, 1024, false, FP) X(1, 256, false, FP) X(1, 512, false, FP) X(1, 1024, false, FP)
+#define RT_FOR_EACH_CONFIG(X) RT_FOR_EACH_SHAPE(X, false) RT_FOR_EACH_SHAPE(X, true)
 
 // ---- the reference's brute-force sweep as a wavefront (BASELINE.json config 5) -------------
 //
@@ -1480,11 +1534,13 @@ hipError_t allow_big_lds(const void* fn) {
 }
 }  // namespace
 
-hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, uint32_t threads, size_t lds_bytes,
-                               uint32_t blocks, hipStream_t stream) {
-#define RT_LAUNCH(M, T, TR)                                                                                    \
-    if (mode == M && threads == T && tris == TR) {                                                            \
-        hipLaunchKernelGGL((rt_pathtrace_kernel<M, T, TR>), dim3(blocks), dim3(T), lds_bytes, stream, ka);    \
+// frame_par: the frame-parallel instance, for a launch rt_path_frame_par_instance (rt_abi.cpp) accepts.
+hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
+                               size_t lds_bytes, uint32_t blocks, hipStream_t stream) {
+    if (frame_par && (!ka.frame_light || ka.accumulate != 1u || ka.bounces == 0)) return hipErrorInvalidValue;
+#define RT_LAUNCH(M, T, TR, FP)                                                                                \
+    if (mode == M && threads == T && tris == TR && frame_par == FP) {                                         \
+        hipLaunchKernelGGL((rt_pathtrace_kernel<M, T, TR, FP>), dim3(blocks), dim3(T), lds_bytes, stream, ka); \
         return hipGetLastError();                                                                             \
     }
     RT_FOR_EACH_CONFIG(RT_LAUNCH)
@@ -1547,18 +1603,18 @@ hipError_t rt_launch_primary(const KernelArgs& ka, int mode, bool tris, size_t l
 // add contention), ties to the smaller workgroup.
 constexpr int kDefaultWavesPerCu = 16;
 
-hipError_t rt_pathtrace_pick_config(int mode, bool tris, size_t lds_bytes, size_t lds_bytes_per_thread,
-                                    uint32_t force_threads, uint32_t waves_cap, uint32_t* threads,
-                                    int* blocks_per_cu) {
+hipError_t rt_pathtrace_pick_config(int mode, bool tris, bool frame_par, size_t lds_bytes,
+                                    size_t lds_bytes_per_thread, uint32_t force_threads, uint32_t waves_cap,
+                                    uint32_t* threads, int* blocks_per_cu) {
     const int kTargetWavesPerCu = waves_cap ? (int)waves_cap : kDefaultWavesPerCu;
     int best_waves = -1;
     // lds_bytes_per_thread: the cooperative leaf batch's per-wave scratch (grows with the workgroup size)
-#define RT_OCC(M, T, TR)                                                                                  \
-    if (mode == M && tris == TR) {                                                                        \
+#define RT_OCC(M, T, TR, FP)                                                                              \
+    if (mode == M && tris == TR && frame_par == FP) {                                                     \
         int n = 0;                                                                                        \
-        hipError_t e = allow_big_lds(reinterpret_cast<const void*>(&rt_pathtrace_kernel<M, T, TR>));     \
+        hipError_t e = allow_big_lds(reinterpret_cast<const void*>(&rt_pathtrace_kernel<M, T, TR, FP>)); \
         if (e != hipSuccess) return e;                                                                    \
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rt_pathtrace_kernel<M, T, TR>, T,           \
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rt_pathtrace_kernel<M, T, TR, FP>, T,       \
                                                          lds_bytes + (size_t)T * lds_bytes_per_thread);  \
         if (e != hipSuccess) return e;                                                                    \
         const int waves = std::min(n * (int)(T / 64), kTargetWavesPerCu);                                 \

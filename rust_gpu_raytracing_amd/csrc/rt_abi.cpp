@@ -30,11 +30,11 @@
 
 hipError_t rt_launch_math_selftest(uint32_t which, unsigned long long* mismatches, uint32_t* first_bad,
                                    hipStream_t stream);
-hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, uint32_t threads, size_t lds_bytes,
-                               uint32_t blocks, hipStream_t stream);
-hipError_t rt_pathtrace_pick_config(int mode, bool tris, size_t lds_bytes, size_t lds_bytes_per_thread,
-                                    uint32_t force_threads, uint32_t waves_cap, uint32_t* threads,
-                                    int* blocks_per_cu);
+hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
+                               size_t lds_bytes, uint32_t blocks, hipStream_t stream);
+hipError_t rt_pathtrace_pick_config(int mode, bool tris, bool frame_par, size_t lds_bytes,
+                                    size_t lds_bytes_per_thread, uint32_t force_threads, uint32_t waves_cap,
+                                    uint32_t* threads, int* blocks_per_cu);
 hipError_t rt_launch_edit(const float* model, const uint32_t* tri_object, const uint32_t* sub_object,
                           const uint2* object_tris, const rt_scene::Placement* place, uint32_t object_count,
                           uint32_t n_tri, uint32_t n_sub, RtTriangleHot* tris, float4* bounds, RtSubObject* subs,
@@ -265,6 +265,8 @@ struct rt_ctx {
     float4* d_tri_qgrid = nullptr;
     size_t qnodes_cap = 0;
     bool batch_schedule = false;      // tuning "batch_schedule" 1: cost-ordered claims in batches too
+    // tuning "frame_par_instance" 0: frame-parallel batches run the generic path kernel instance too
+    bool frame_par_instance = true;
     // a tile's frames claimed one after another (C3 -12%, C4 -8%, C5 -4%, C2 -1.8% per frame
     // against frame-major, profiles/archive/r02_knobs2); tuning "unit_tile_major" 0: frame-major
     bool unit_tile_major = true;
@@ -285,6 +287,14 @@ struct rt_ctx {
     size_t occ_lds_bytes = 0;
     int occ_mode = -1;
     bool occ_tris = false;
+    // the occupancy query's answer per path kernel instance (0 generic, 1 frame-parallel), so that a
+    // context whose launches alternate instances (full batches and a one-frame remainder) asks once each
+    struct OccEntry {
+        size_t lds_bytes = 0, stack_pt = 0;
+        int mode = -1, blocks_per_cu = 0;
+        bool tris = false;
+        uint32_t threads = 0, force_threads = 0, waves_cap = 0;
+    } occ_cache[2];
     size_t occ_stack_pt = 0;
     int max_lds_mode = 2;               // tuning "lds_mode": highest staging mode allowed
     int occ_blocks_per_cu = 0;
@@ -1484,6 +1494,16 @@ static int scene_accel_args(rt_ctx* ctx, KernelArgs& ka, SceneLaunch& sl) {
     return RT_OK;
 }
 
+// Which instance of the path kernel a launch runs (the one place that decides it): the
+// frame-parallel instance (pathtrace.hip, kFramePar) for a frame-parallel batch -- accumulating,
+// its lights within kMaxParallelLights -- that traces at least one segment per sample; the
+// generic instance for every other launch (non-accumulating, "frame_parallel" 0, a batch past
+// the light limit, bounces == 0: its samples end in setup, which only the generic instance
+// handles) and when the tuning key "frame_par_instance" is 0.
+static bool rt_path_frame_par_instance(bool frame_par_batch, uint32_t accumulate, uint32_t bounces, bool enabled) {
+    return enabled && frame_par_batch && accumulate == 1u && bounces >= 1u;
+}
+
 // One launch rendering `frames` frames starting at Params.accumulation_index.
 static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     const rt_params& p = ctx->params;
@@ -1543,7 +1563,9 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
         }
         ka.queue_units = ctx->owned_tiles * frames;
         ka.unit_tile_major = ctx->unit_tile_major ? 1u : 0u;
+        ka.light_plane = (uint32_t)owned_px;
     }
+    const bool fp_instance = rt_path_frame_par_instance(frame_par, p.accumulate, bounces, ctx->frame_par_instance);
 
     SceneLaunch sl;
     scene_carve(ctx, ka, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
@@ -1631,20 +1653,30 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     const size_t lane_pt = coop ? (size_t)kLeafBatchWaveBytes / 64u : 0u;
     // Persistent grid: as many workgroups as can be resident (never more than
     // one wave per tile); waves then pull tiles from the queue.
-    if (ctx->occ_blocks_per_cu == 0 || ctx->occ_lds_bytes != lds_bytes || ctx->occ_mode != mode ||
-        ctx->occ_tris != tris || ctx->occ_stack_pt != lane_pt) {
+    rt_ctx::OccEntry& oc = ctx->occ_cache[fp_instance ? 1 : 0];
+    if (oc.blocks_per_cu == 0 || oc.lds_bytes != lds_bytes || oc.mode != mode || oc.tris != tris ||
+        oc.stack_pt != lane_pt || oc.force_threads != ctx->force_threads || oc.waves_cap != ctx->waves_cap) {
         int per_cu = 0;
         uint32_t threads = 0;
-        hipError_t oe = rt_pathtrace_pick_config(mode, tris, lds_bytes, lane_pt, ctx->force_threads, ctx->waves_cap,
-                                                 &threads, &per_cu);
+        hipError_t oe = rt_pathtrace_pick_config(mode, tris, fp_instance, lds_bytes, lane_pt, ctx->force_threads,
+                                                 ctx->waves_cap, &threads, &per_cu);
         if (oe != hipSuccess) return hip_fail(ctx, "rt_pathtrace_pick_config (occupancy query)", oe);
-        ctx->occ_blocks_per_cu = per_cu;
-        ctx->occ_threads = threads;
-        ctx->occ_lds_bytes = lds_bytes;
-        ctx->occ_mode = mode;
-        ctx->occ_tris = tris;
-        ctx->occ_stack_pt = lane_pt;
+        oc.blocks_per_cu = per_cu;
+        oc.threads = threads;
+        oc.lds_bytes = lds_bytes;
+        oc.mode = mode;
+        oc.tris = tris;
+        oc.stack_pt = lane_pt;
+        oc.force_threads = ctx->force_threads;
+        oc.waves_cap = ctx->waves_cap;
     }
+    // this launch's configuration (rt_launch_config reports it)
+    ctx->occ_blocks_per_cu = oc.blocks_per_cu;
+    ctx->occ_threads = oc.threads;
+    ctx->occ_lds_bytes = lds_bytes;
+    ctx->occ_mode = mode;
+    ctx->occ_tris = tris;
+    ctx->occ_stack_pt = lane_pt;
     // the leaf batch scratch after the scene image and its tail
     ka.lds_leafbatch_offset = (uint32_t)al16(lds_bytes);
     if (coop) lds_bytes = ka.lds_leafbatch_offset + (size_t)ctx->occ_threads * lane_pt;
@@ -1760,9 +1792,10 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
         RT_HIP(ctx, rt_launch_primary(pka, mode, tris, image, mode == 2 ? 1024u : ctx->primary_threads, min_waves, S));
         ka.primary = pka.primary;
     }
-    hipError_t e = rt_launch_pathtrace(ka, mode, tris, ctx->occ_threads, lds_bytes, blocks, S);
+    hipError_t e = rt_launch_pathtrace(ka, mode, tris, fp_instance, ctx->occ_threads, lds_bytes, blocks, S);
     ctx->last_blocks = blocks;
-    ctx->last_passes = RT_PASS_PATH | (primary ? RT_PASS_PRIMARY : 0u) | (frame_par ? RT_PASS_RESOLVE : 0u);
+    ctx->last_passes = RT_PASS_PATH | (primary ? RT_PASS_PRIMARY : 0u) | (frame_par ? RT_PASS_RESOLVE : 0u) |
+                       (fp_instance ? RT_PASS_PATH_FRAME_PAR : 0u);
     ctx->last_lds = (uint32_t)lds_bytes;
     if (e != hipSuccess) return hip_fail(ctx, "rt_pathtrace_kernel launch", e);
     if (frame_par) {
@@ -2878,6 +2911,8 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         rc = flag(ctx->batch_schedule);
     } else if (k == "unit_tile_major") {
         rc = flag(ctx->unit_tile_major);
+    } else if (k == "frame_par_instance") {
+        rc = flag(ctx->frame_par_instance);
     } else if (k == "query_chunk") {
         if ((rc = range(1, (int32_t)kMaxQueryChunk)) == RT_OK) ctx->query_chunk = (uint32_t)v;
     } else if (k == "gather_chunk") {

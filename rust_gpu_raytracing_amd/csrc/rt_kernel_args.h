@@ -252,4 +252,7 @@ struct KernelArgs {
     uint32_t lds_sub_offset;  // mode 2: sub-object records staged in LDS at this offset; 0: read from global
     uint32_t lds_stack_offset;    // brute force: the sub-object tiles and hit lists after the scene image
     uint32_t lds_srgb_offset;
+    // frame-parallel batches: float4 entries of one (frame, sample) plane of frame_light,
+    // owned_tiles * 64, computed by the host once per launch
+    uint32_t light_plane;
 };

@@ -394,8 +394,21 @@ __device__ __forceinline__ HitId trace_end_id(const TraceState& ts) {
     return HitId{0u, 0u, 0u};
 }
 
+// The launch constants that shading reads (shade, sample_env, fetch_texture), under KernelArgs'
+// names. Those functions take either block: the frame-parallel instance of the path kernel
+// (pathtrace.hip) fills this one from the kernel-argument segment where a pass shades, so that
+// the constants are not kept in (and spilled from) scalar registers across its outer loop.
+struct ShadeArgs {
+    const uint32_t* __restrict__ textures;
+    const uint32_t* __restrict__ env;
+    uint32_t texture_width, texture_height, env_map_width, env_map_height, material_count;
+    uint32_t tex_w, tex_h, tex_layers, env_w, env_h, env_uniform;
+    uint32_t bounces;
+};
+
 // sample_texture, compute_shader.wgsl:26-32: the raw RGBA8 texel (decoded later).
-__device__ __forceinline__ uint32_t fetch_texture(const KernelArgs& ka, uint32_t layer, float u, float v) {
+template <class KA>
+__device__ __forceinline__ uint32_t fetch_texture(const KA& ka, uint32_t layer, float u, float v) {
     const int x = texel_coord(u * (float)(int32_t)ka.texture_width, ka.tex_w);
     const int y = texel_coord(v * (float)(int32_t)ka.texture_height, ka.tex_h);
     const uint32_t l = min(layer, ka.tex_layers - 1u);
@@ -403,7 +416,8 @@ __device__ __forceinline__ uint32_t fetch_texture(const KernelArgs& ka, uint32_t
     return ka.textures[off];
 }
 
-__device__ __forceinline__ f4 sample_env(const KernelArgs& ka, const float* srgb, f3 d) {
+template <class KA>
+__device__ __forceinline__ f4 sample_env(const KA& ka, const float* srgb, f3 d) {
     // environment_map_coords, :580-585. A coordinate is computed only when the
     // texel depends on it: with every row (column) of the map one colour, any u
     // (v) -- NaN included -- fetches the same texel as column (row) 0.
@@ -494,8 +508,8 @@ __device__ __forceinline__ void start_sample_at(f3 origin, uint32_t stream, uint
 // environment, or the bounce limit is reached).
 // kAux: the material's glass constants come from the LDS table staged with the
 // materials (same f32 operations, computed once per workgroup instead of per hit).
-template <bool kAux>
-__device__ __forceinline__ bool shade(const SceneView& sv, const KernelArgs& ka, Path& p, const Hit& h) {
+template <bool kAux, class KA>
+__device__ __forceinline__ bool shade(const SceneView& sv, const KA& ka, Path& p, const Hit& h) {
     if (h.t == kF32Max) {
         const f4 c = sample_env(ka, sv.srgb, p.d);
         p.light.x = p.light.x + c.x * p.contrib.x;

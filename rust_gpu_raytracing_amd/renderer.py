@@ -838,11 +838,17 @@ class Renderer:
         N.check(self._ctx, self._lib.rt_launch_config(self._ctx, *[ctypes.byref(x) for x in v]), self._lib)
         return dict(zip(("threads", "blocks", "lds_bytes", "scene_in_lds"), (x.value for x in v)))
 
+    def last_launch_pass_mask(self) -> int:
+        """The raw RT_PASS_* mask of the last launch (include/rt_abi.h): what last_launch_passes()
+        names, plus RT_PASS_PATH_FRAME_PAR when the path kernel ran as its frame-parallel instance."""
+        v = ctypes.c_uint32()
+        N.check(self._ctx, self._lib.rt_last_launch_passes(self._ctx, ctypes.byref(v)), self._lib)
+        return v.value
+
     def last_launch_passes(self) -> list:
         """Kernels the last launch ran: "path", "primary" (pre-pass), "resolve", "brute",
         "brute_stream" (the brute-force sweep's scalar-cache variant)."""
-        v = ctypes.c_uint32()
-        N.check(self._ctx, self._lib.rt_last_launch_passes(self._ctx, ctypes.byref(v)), self._lib)
+        v = ctypes.c_uint32(self.last_launch_pass_mask())
         names = ((N.RT_PASS_PATH, "path"), (N.RT_PASS_PRIMARY, "primary"), (N.RT_PASS_RESOLVE, "resolve"),
                  (N.RT_PASS_BRUTE, "brute"), (N.RT_PASS_BRUTE_STREAM, "brute_stream"))
         return [n for bit, n in names if v.value & bit]

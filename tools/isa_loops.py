@@ -38,6 +38,11 @@ WRITELANE = re.compile(r"^\s+v_writelane_b32\s+(v\d+),")
 READLANE = re.compile(r"^\s+v_readlane_b32\s+s\[?\d+(?::\d+\])?,\s*(v\d+),")
 
 
+def is_branch(mn):
+    """One definition for the section and whole-kernel counts: conditional, unconditional and indirect branches."""
+    return mn.startswith("s_cbranch") or mn in ("s_branch", "s_setpc_b64")
+
+
 def compile_asm(out: Path, marks: bool):
     cmd = ["/opt/rocm/bin/hipcc", *FLAGS, *(["-DRT_ISA_MARKS"] if marks else []), "-o", str(out), "-I", str(ROOT / "include"),
            "-I", str(ROOT / "rust_gpu_raytracing_amd/csrc"), str(ROOT / "rust_gpu_raytracing_amd/csrc/pathtrace.hip")]
@@ -133,7 +138,26 @@ def analyse(body):
             r["spill_readlanes"] += bool(rl and rl.group(1) in spill)
         r["labels"] = sum(1 for j in range(i + 1, end) if LABEL.match(body[j]))  # 0: nothing jumps into it
         regions.append(r)
-    return spill, out, total_rl, marks, regions
+    # outer-loop sections: the text from a "shade", "refill" or "setup" marker to the next marker of
+    # any name (they follow one another in the outer loop; the text order is the compiler's, so a
+    # section's tail can hold a block of its neighbour: read the three together as the outer loop's cost)
+    sections = []
+    for k, (i, tag) in enumerate(tags):
+        if tag not in ("shade", "refill", "setup"):
+            continue
+        end = tags[k + 1][0] if k + 1 < len(tags) else len(body)
+        sec = dict(tag=tag, insts=0, valu=0, salu=0, branches=0, readlanes=0, writelanes=0)
+        for j, mn in insts:
+            if not i < j < end:
+                continue
+            sec["insts"] += 1
+            sec["valu"] += mn.startswith("v_")
+            sec["branches"] += is_branch(mn)
+            sec["salu"] += mn.startswith("s_") and mn not in ("s_waitcnt", "s_nop") and not is_branch(mn)
+            sec["readlanes"] += mn == "v_readlane_b32"
+            sec["writelanes"] += mn == "v_writelane_b32"
+        sections.append(sec)
+    return spill, out, total_rl, marks, regions, sections
 
 
 def main():
@@ -154,9 +178,12 @@ def main():
     for name, body in functions(text.splitlines()):
         if args.kernel not in name:
             continue
-        spill, loops, total_rl, marks, regions = analyse(body)
+        spill, loops, total_rl, marks, regions, sections = analyse(body)
+        # (assembly of a commit before the frame-parallel instances, --asm: no fourth parameter)
         short = re.sub(r"_Z19rt_pathtrace_kernelILi(\d)ELj(\d+)ELb([01])EEv10KernelArgs",
                        r"pathtrace<mode \1, \2 threads, tris \3>", name)
+        short = re.sub(r"_Z19rt_pathtrace_kernelILi(\d)ELj(\d+)ELb([01])ELb([01])EEv10KernelArgs",
+                       r"pathtrace<mode \1, \2 threads, tris \3, frame_par \4>", short)
         print(f"{short}: spill VGPRs {sorted(spill)}, spill reloads in the kernel {total_rl}")
         for tag, lp in sorted(marks.items()):
             print("  {tag:10s} innermost loop around it: insts {insts:5d} valu {valu:5d} spill_readlanes {spill_readlanes:3d}".format(
@@ -164,6 +191,16 @@ def main():
         for r in regions:
             print("  {tag:10s} region to {tag}_end: insts {insts:4d} valu {valu:4d} salu {salu:3d} lds {lds:3d} waits {waits:3d} "
                   "branches {branches:2d} labels {labels:2d} spill_readlanes {spill_readlanes:2d}".format(**r))
+        for sec in sections:
+            print("  {tag:10s} section to the next marker: insts {insts:4d} valu {valu:4d} salu {salu:4d} branches {branches:3d} "
+                  "v_readlane {readlanes:3d} v_writelane {writelanes:3d}".format(**sec))
+        body_insts = [INST.match(ln).group(1) for ln in body
+                      if INST.match(ln) and not ln.strip().startswith((";", "."))]
+        print("  whole kernel: insts {} valu {} v_readlane {} v_writelane {} s_nop {} s_and_saveexec {} branches {}".format(
+            len(body_insts), sum(m.startswith("v_") for m in body_insts), body_insts.count("v_readlane_b32"),
+            body_insts.count("v_writelane_b32"), body_insts.count("s_nop"),
+            sum(m.startswith("s_and_saveexec") for m in body_insts),
+            sum(is_branch(m) for m in body_insts)))
         for lp in loops if args.all_loops else []:
             if lp["insts"] < args.min_insts:
                 continue

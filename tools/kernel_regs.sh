@@ -15,7 +15,7 @@ case "$1" in *.hip) src=$1; shift ;; esac
   sed -E 's/.*remark: //' | paste - - - - - - |
   if [ "$src" = pathtrace.hip ]; then
     grep pathtrace_kernel |
-    sed -E "s/ \[-Rpass-analysis=kernel-resource-usage\]//g; s/Function Name: _Z19rt_pathtrace_kernelIL(i[0-9])ELj([0-9]+)ELb([01])EEv10KernelArgs/mode \1 threads \2 tris \3/; s/[[:space:]]+/ /g"
+    sed -E "s/ \[-Rpass-analysis=kernel-resource-usage\]//g; s/Function Name: _Z19rt_pathtrace_kernelIL(i[0-9])ELj([0-9]+)ELb([01])ELb([01])EEv10KernelArgs/mode \1 threads \2 tris \3 frame_par \4/; s/[[:space:]]+/ /g"
   else
     sed -E "s/ \[-Rpass-analysis=kernel-resource-usage\]//g; s/Function Name: _Z[0-9]+(rt_[a-z_]+)IL(i[0-9])ELb([01])ELj([0-9]+)ELb([01])EEv10KernelArgs[0-9A-Za-z]+/\1 mode \2 tris \3 threads \4 gather \5/; s/Function Name: _Z[0-9]+(rt_[a-z_]+)IL(i[0-9])ELb([01])ELj([0-9]+)EEv10KernelArgs[0-9A-Za-z]+/\1 mode \2 tris \3 threads \4/"
   fi
