@@ -59,11 +59,15 @@ def oracle_radiance(O, scene, rays, streams, bounces, first_sample, samples):
     p = scene.params(accumulate=1, compute_per_frame=samples, accumulation_index=first_sample)
     want = np.zeros((n, 4), np.float32)
     segs = np.zeros(n, np.int64)
-    for j in range(n):
-        origin[:] = rays[j, :3]
-        acc, _, cnt = o.render_pixels(p, bounces, [int(streams[j])], threads=1)
-        want[j] = acc[0]
-        segs[j] = cnt
+    camera_origin = origin.copy()  # (the array may be the scene's own camera position)
+    try:
+        for j in range(n):
+            origin[:] = rays[j, :3]
+            acc, _, cnt = o.render_pixels(p, bounces, [int(streams[j])], threads=1)
+            want[j] = acc[0]
+            segs[j] = cnt
+    finally:
+        origin[:] = camera_origin
     return want, segs
 
 
