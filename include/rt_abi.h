@@ -54,7 +54,8 @@ extern "C" {
  * rt_temporal_default_params, rt_temporal_params);
  * 12, additive: gather queries (rt_gather, rt_gather_device, rt_gather_point);
  * 12, additive: display transform (rt_display, rt_read_display, rt_copy_display_to_device,
- * rt_display_state, rt_display_reset, rt_display_default_params, rt_display_params). */
+ * rt_display_state, rt_display_reset, rt_display_default_params, rt_display_params);
+ * 12, additive: probe queries (rt_probe_sh, rt_probe_sh_device, rt_probe). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -606,6 +607,99 @@ RT_API int rt_gather_device(rt_ctx* ctx, const void* points_device, void* radian
                             uint32_t bounces, uint32_t first_sample, uint32_t samples,
                             void* segments_device /* may be NULL; one u64, added to */);
 
+/* ---- probe queries (ABI 12, additive: probe queries) ------------------------
+ *
+ * "What light arrives at this point in free space, from every direction?": per probe, the
+ * projection of the incoming light onto the nine second-order spherical harmonics, per colour
+ * channel, from `samples` paths that leave the point in uniform directions. Irradiance and
+ * reflection probes for dynamic objects, which look the probe up with whatever normal they have
+ * at the time: a few to a few thousand probes with hundreds to thousands of samples each. The
+ * directions are drawn on the device with the reference's RNG, every (probe, sample) path is a
+ * work item of its own, and the reduction order is stated, so every value is bit-exact and
+ * independent of placement and schedule. */
+
+/* {position, stream}: one 16-byte load. */
+typedef struct rt_probe {
+    float position[3];
+    uint32_t stream;  /* takes the place of the pixel index in the seeds; use streams >= 1 */
+} rt_probe;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_probe) == 16, "rt_probe is 16 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_probe) == 16, "rt_probe is 16 bytes");
+#endif
+
+/* Writes 36 floats per probe, in order: coefficient k = 0 .. 8 at floats [4k, 4k + 4) as rgba;
+ * nothing outside [0, 36 * count) is written.
+ *
+ * THE PROBE CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+ * written order, with no contraction. For probe i with record (x, stream):
+ *  1. Sample index. For s = 0 .. samples-1, u = first_sample + s (u32, wrapping).
+ *  2. Direction. dseed = (stream * u * 326624u) ^ 0x9E3779B9u (u32, wrapping).
+ *     gx, gy, gz = normal_distribution(&dseed) three times, in that order
+ *     (compute_shader.wgsl:622-628, theta drawn before rho).
+ *     dir = normalize((gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and
+ *     dot(v, v) = (x*x + y*y) + z*z: a uniform direction on the sphere.
+ *  3. Path. L_s is the result rt_radiance defines for the record (x, stream, dir) with
+ *     first_sample = u, samples = 1 and the call's bounces. The origin is x as given (no offset).
+ *  4. Basis, on dir = (dx, dy, dz) of step 2 (before per_pixel's jitter):
+ *     b0 = 0.28209479f                       b1 = 0.48860251f * dy
+ *     b2 = 0.48860251f * dz                  b3 = 0.48860251f * dx
+ *     b4 = 1.09254843f * (dx*dy)             b5 = 1.09254843f * (dy*dz)
+ *     b6 = 0.31539157f * (3.0f*(dz*dz) - 1.0f)
+ *     b7 = 1.09254843f * (dx*dz)             b8 = 0.54627422f * (dx*dx - dy*dy)
+ *     T_{s,k} = L_s * b_k: one multiply per channel, all four channels.
+ *  5. Reduction, for each k = 0 .. 8 on its own: P_j (j = 0 .. 63) starts at +0.0f. For s ascending,
+ *     P_{s mod 64} = P_{s mod 64} + T_{s,k}. Then, for off = 32, 16, 8, 4, 2, 1:
+ *     P_j = P_j + P_{j+off} for every j < off. sh[i][k] = P_0. Lanes that got no sample take part
+ *     with +0.0f.
+ * End of the probe contract.
+ *
+ * Consequences:
+ *  - The caller multiplies by 4 pi / `samples` to get the radiance coefficients (the directions
+ *    are uniform, with density 1 / 4 pi). Nothing is clamped.
+ *  - bounces == 0 gives all-zero coefficients and no segments, and is RT_OK. samples == 0 is
+ *    RT_E_INVALID (whatever `count` is), and so is `samples` above 16777216: one probe's
+ *    scratch is then 256 MB, the most the call will allocate.
+ *  - Stream 0 makes both seeds constant, so it draws the same sample every time: callers use
+ *    streams >= 1.
+ *  - A draw of exactly 0 makes rho infinite, as in the reference; the result is then
+ *    unspecified.
+ *  - Where no drawn component gx, gy, gz is +-0, a probe's L_s is bit for bit the L_s of a gather
+ *    point at x with normal (0, 0, 0) (rt_gather's steps 1 to 3 with n = 0).
+ *  - The exactness domain and the termination argument are those of the radiance queries: a
+ *    lane runs at most `bounces` walks per (probe, sample) it takes.
+ *  - *segments receives the call's counted ray segments under the rule of rt_radiance; in the
+ *    device variant the kernel adds the total into the caller's u64 (added to, not set).
+ *
+ * Scene visibility and side effects are those of rt_gather: the query sees the scene as of the
+ * call and changes nothing a render can observe. It works on rank contexts (world_size > 1).
+ *
+ * Both entry points run in launches of at most tuning "probe_chunk" paths, but of whole probes:
+ * max(1, probe_chunk / samples) probes per launch. The lights L_s of a launch live in a buffer
+ * the context owns, 16 bytes per path (16 MB at the default), allocated on first use and freed by
+ * rt_destroy. A call of more than one launch keeps two in flight, on the context's two streams,
+ * each with its own half of a buffer of twice that size (32 MB at the default), where that stays
+ * within 256 MB; rt_stream(ctx) is ordered after both before the call returns.
+ * rt_probe_sh: host pointers, synchronous. Staged through the pinned buffer of rt_trace_rays
+ * in chunks of tuning "query_chunk" probes (16 bytes in, 144 bytes out per probe). `segments`
+ * may be NULL.
+ * rt_probe_sh_device: device pointers on the context's device; probes and sh 16-byte aligned,
+ * segments_device (may be NULL) 8-byte aligned; stream-ordered on rt_stream(ctx), no host copy,
+ * asynchronous. RT_E_INVALID when any of them is not device memory of the context's device, as
+ * for rt_gather_device.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries; by default
+ * calls of fewer than 262144 walks (count * samples) read the scene from global memory.
+ * count == 0 returns RT_OK and launches nothing; a NULL probes or sh pointer with count > 0 is
+ * RT_E_INVALID. */
+RT_API int rt_probe_sh(rt_ctx* ctx, const rt_probe* probes, float* sh /* 36 floats per probe: 9 x rgba */,
+                       uint64_t count, uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                       uint64_t* segments /* may be NULL */);
+RT_API int rt_probe_sh_device(rt_ctx* ctx, const void* probes_device, void* sh_device, uint64_t count,
+                              uint32_t bounces, uint32_t first_sample, uint32_t samples,
+                              void* segments_device /* may be NULL; one u64, added to */);
+
 /* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
  *
  * What an interactive host shows right after the camera or the scene moved: the reference resets
@@ -1079,7 +1173,9 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays, rt_occluded and rt_radiance),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
  *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does),
- *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather and rt_gather_device, 1 KB of partials each);
+ *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather and rt_gather_device, 1 KB of partials each),
+ *   "probe_chunk" 1048576 (1..2^26: paths per launch of rt_probe_sh and rt_probe_sh_device, 16 B of scratch each;
+ *   a launch covers whole probes, max(1, probe_chunk / samples) of them);
  *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),
  *   "denoise_lds" 1|0 (1: the filter passes with step 1 and 2 stage tile + halo in LDS, 0: direct loads).
  * RT_E_INVALID for an unknown key or a value out of range. */

@@ -3,7 +3,7 @@
 ``compute_shader.wgsl`` is a hand-written gfx950 HIP kernel behind the C ABI in
 ``include/rt_abi.h``; :class:`Renderer` mirrors ``src/renderer.rs`` on top of it.
 """
-from . import buffers
+from . import buffers, sh
 from ._native import NativeLibraryError, RtError, load_library
 from .camera import Camera
 from .renderer import REFERENCE_BOUNCES, Renderer
@@ -20,4 +20,5 @@ __all__ = [
     "RtError",
     "build_config",
     "load_library",
+    "sh",
 ]

@@ -98,6 +98,10 @@ class rt_gather_point(ctypes.Structure):
                 ("normal", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
 
 
+class rt_probe(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_float * 3), ("stream", ctypes.c_uint32)]
+
+
 class rt_hit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
                 ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
@@ -130,6 +134,7 @@ assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
 assert ctypes.sizeof(rt_radiance_ray) == 32
 assert ctypes.sizeof(rt_gather_point) == 32 and rt_gather_point.stream.offset == 12 and rt_gather_point.normal.offset == 16
+assert ctypes.sizeof(rt_probe) == 16 and rt_probe.stream.offset == 12
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -173,6 +178,8 @@ SIGNATURES = {
     "rt_radiance_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_gather": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_gather_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
+    "rt_probe_sh": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_probe_sh_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_denoise_default_params":(ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
     "rt_compute_features": (ctypes.c_int, [_P]),
     "rt_read_features": (ctypes.c_int, [_P, _P, _P]),

@@ -26,7 +26,7 @@
 //    reduced once per wave at exit and added to the caller's counter with one atomic per wave.
 //
 // Gather queries (rt_gather, rt_gather_device) run on the same kernel body,
-// instantiated with kGather, and on rt_gather_resolve_kernel below. The contract, as in
+// instantiated with kPathGather, and on rt_gather_resolve_kernel below. The contract, as in
 // include/rt_abi.h:
 //
 // THE GATHER CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
@@ -57,6 +57,43 @@
 //  * rt_gather_resolve_kernel runs step 4's tree: one wave per point, lane j loads P_j (one
 //    coalesced 1 KB read; +0.0f for a stripe the point does not have), six shuffle levels in the
 //    contract's order, one 16-B store.
+//
+// Probe queries (rt_probe_sh, rt_probe_sh_device) run on the same kernel body,
+// instantiated with kPathProbe, and on rt_probe_resolve_kernel below. The contract, as in
+// include/rt_abi.h:
+//
+// THE PROBE CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+// written order, with no contraction. For probe i with record (x, stream):
+//  1. Sample index. For s = 0 .. samples-1, u = first_sample + s (u32, wrapping).
+//  2. Direction. dseed = (stream * u * 326624u) ^ 0x9E3779B9u (u32, wrapping).
+//     gx, gy, gz = normal_distribution(&dseed) three times, in that order
+//     (compute_shader.wgsl:622-628, theta drawn before rho).
+//     dir = normalize((gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and
+//     dot(v, v) = (x*x + y*y) + z*z: a uniform direction on the sphere.
+//  3. Path. L_s is the result rt_radiance defines for the record (x, stream, dir) with
+//     first_sample = u, samples = 1 and the call's bounces. The origin is x as given (no offset).
+//  4. Basis, on dir = (dx, dy, dz) of step 2 (before per_pixel's jitter):
+//     b0 = 0.28209479f                       b1 = 0.48860251f * dy
+//     b2 = 0.48860251f * dz                  b3 = 0.48860251f * dx
+//     b4 = 1.09254843f * (dx*dy)             b5 = 1.09254843f * (dy*dz)
+//     b6 = 0.31539157f * (3.0f*(dz*dz) - 1.0f)
+//     b7 = 1.09254843f * (dx*dz)             b8 = 0.54627422f * (dx*dx - dy*dy)
+//     T_{s,k} = L_s * b_k: one multiply per channel, all four channels.
+//  5. Reduction, for each k = 0 .. 8 on its own: P_j (j = 0 .. 63) starts at +0.0f. For s ascending,
+//     P_{s mod 64} = P_{s mod 64} + T_{s,k}. Then, for off = 32, 16, 8, 4, 2, 1:
+//     P_j = P_j + P_{j+off} for every j < off. sh[i][k] = P_0. Lanes that got no sample take part
+//     with +0.0f.
+// End of the probe contract.
+//
+//  * The work item is a (probe, sample) pair: item t of a launch is sample t % samples of probe
+//    t / samples, dealt in chunks as a radiance query's rays are. The lane runs that one path and
+//    stores L_s to slot t of the launch's scratch (one 16-B store): no sample loop, no sum, so a
+//    lane that finishes a short path takes the next item instead of waiting for a stripe.
+//  * rt_probe_resolve_kernel runs steps 4 and 5: one wave per probe, lane j walks s = j, j + 64,
+//    ... (step 5's P_j), loads L_s (1 KB per step across the wave), draws step 2's direction
+//    again from (stream, u) with the path kernel's own function -- the scratch holds no
+//    directions: 16 B per path, not 32 -- and adds the 36 products in sample order; then six
+//    shuffle levels on each of the 36 values and nine 16-B stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -81,16 +118,33 @@ struct RadianceArgs {
     unsigned long long claimed_from;            // first ray handed out by the counter: first_chunk x the launch's waves
     uint32_t first_sample;                      // random_index of a ray's first sample (:154)
     uint32_t samples;                           // samples per ray, >= 1 (ka.bounces >= 1 too: the host answers 0)
-    uint32_t stripes;                           // kGather: stripes per point, min(samples, 64)
+    uint32_t stripes;                           // kPathGather: stripes per point, min(samples, 64)
 };
 
-// kGather: the path kernel of a gather query (the contract above). A "ray" is then a (point,
-// stripe) item: qa.rays holds rt_gather_point records, qa.count the launch's items (points x
+// What the body of rt_radiance_kernel answers.
+enum PathKind : int { kPathRadiance = 0, kPathGather = 1, kPathProbe = 2 };
+
+// Step 2 of the probe contract: the direction of the sample with index u of a probe's stream. The
+// path kernel and the resolve kernel both call this, so both hold the same bits.
+__device__ __forceinline__ f3 probe_direction(uint32_t stream, uint32_t u) {
+    uint32_t dseed = (stream * u * 326624u) ^ 0x9E3779B9u;
+    const float gx = normal01(dseed);
+    const float gy = normal01(dseed);
+    const float gz = normal01(dseed);
+    return normalize(mk(gx, gy, gz));
+}
+
+// kPathGather: the path kernel of a gather query (the gather contract above). A "ray" is then a
+// (point, stripe) item: qa.rays holds rt_gather_point records, qa.count the launch's items (points x
 // qa.stripes, below 2^32), and qa.radiance the partials, 64 float4 per point.
-template <int kMode, bool kTris, uint32_t kThreads, bool kGather = false>
+// kPathProbe: the path kernel of a probe query (the probe contract above). A "ray" is a (probe,
+// sample) item: qa.rays holds rt_probe records, 16 B each, qa.count the launch's items (probes x
+// qa.samples, below 2^32), and qa.radiance the scratch, one float4 per item.
+template <int kMode, bool kTris, uint32_t kThreads, PathKind kKind = kPathRadiance>
 __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka, RadianceArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool kAux = kMode >= 1;
+    constexpr bool kGather = kKind == kPathGather, kProbe = kKind == kPathProbe;
     // The path kernel's LDS image without the camera block: what the walk, the record and shading
     // read.
     SceneView sv = global_scene_view<kMode, kTris>(ka, ka.srgb);
@@ -119,8 +173,14 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
     // cache) instead of holding origin, direction and stream in 7 registers through every walk.
     // kGather: `ray` is point * 64 + stripe (the item's slot among the partials) and `sample` the
     // sample index s; the origin and the direction are steps 1 and 2 of the contract.
+    // kProbe: `ray` is the item t; one 16-B load reads the probe's record.
     auto begin_sample = [&]() {
-        if constexpr (kGather) {
+        if constexpr (kProbe) {
+            const uint32_t probe = (uint32_t)ray / qa.samples, s = (uint32_t)ray - probe * qa.samples;
+            const float4 r0 = qa.rays[probe];
+            const uint32_t stream = __float_as_uint(r0.w), u = qa.first_sample + s;
+            start_sample_at(mk(r0.x, r0.y, r0.z), stream, u, probe_direction(stream, u), p);
+        } else if constexpr (kGather) {
             const float4 r0 = qa.rays[2ull * (ray >> 6)], r1 = qa.rays[2ull * (ray >> 6) + 1ull];
             const f3 n = mk(r1.x, r1.y, r1.z);
             const uint32_t stream = __float_as_uint(r0.w), u = qa.first_sample + sample;
@@ -147,7 +207,15 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
         if (mode == kDone) {
             const Hit h = trace_end<kTris>(sv, ka, p.o, p.d, ts);
             ++segs;
-            if (shade<kAux>(sv, ka, p, h)) {
+            if constexpr (kProbe) {
+                // the item's one path: L_s = +0.0f + light, the sum of a radiance query of one sample
+                if (shade<kAux>(sv, ka, p, h)) {
+                    qa.radiance[ray] = make_float4(0.0f + p.light.x, 0.0f + p.light.y, 0.0f + p.light.z, 0.0f + p.light.w);
+                    mode = kIdle;
+                } else {
+                    mode = kSetup;
+                }
+            } else if (shade<kAux>(sv, ka, p, h)) {
                 sum.x = sum.x + p.light.x;
                 sum.y = sum.y + p.light.y;
                 sum.z = sum.z + p.light.z;
@@ -178,7 +246,9 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
             if (mode == kIdle) {
                 const uint32_t rank = rank_among(need);
                 if (rank < avail) {
-                    if constexpr (kGather) {
+                    if constexpr (kProbe) {
+                        ray = c.next + rank;
+                    } else if constexpr (kGather) {
                         const uint32_t item = (uint32_t)(c.next + rank), point = item / qa.stripes;
                         sample = item - point * qa.stripes;
                         ray = (unsigned long long)point * 64u + sample;
@@ -236,37 +306,109 @@ __global__ void __launch_bounds__(kResolveThreads) rt_gather_resolve_kernel(cons
     if (lane == 0) radiance[point] = v;
 }
 
-// The instances, (mode, triangles, threads), each also as the gather instance: f(kernel, threads)
-// for the one of (mode, tris, gather). Workgroup size by placement: the global-memory instance has
+// Steps 4 and 5 of a probe query: one wave per probe. Lane j adds the products of the samples
+// j, j + 64, ... in ascending order into its 36 accumulators (step 5's P_j of the nine
+// coefficients, four channels each), drawing each sample's direction again (probe_direction: the
+// path kernel's bits). Then the tree as in rt_gather_resolve_kernel, on each of the 36 values, and
+// lane 0 stores the probe's nine float4. `lights`: the launch's scratch, L_s of probe p at
+// p * samples + s (points * samples is below 2^32).
+__global__ void __launch_bounds__(kResolveThreads) rt_probe_resolve_kernel(const float4* __restrict__ lights,
+                                                                          const float4* __restrict__ probes,
+                                                                          float4* __restrict__ sh, uint32_t count,
+                                                                          uint32_t first_sample, uint32_t samples) {
+    const uint32_t probe = blockIdx.x * (kResolveThreads / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (probe >= count) return;  // wave-uniform
+    const uint32_t stream = __float_as_uint(probes[probe].w);
+    const float4* __restrict__ mine = lights + (size_t)probe * samples;
+    float acc[9][4];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0.0f;
+    for (uint32_t s = lane; s < samples; s += 64u) {
+        const float4 l = mine[s];
+        const f3 d = probe_direction(stream, first_sample + s);
+        const float b[9] = {0.28209479f,
+                            0.48860251f * d.y,
+                            0.48860251f * d.z,
+                            0.48860251f * d.x,
+                            1.09254843f * (d.x * d.y),
+                            1.09254843f * (d.y * d.z),
+                            0.31539157f * (3.0f * (d.z * d.z) - 1.0f),
+                            1.09254843f * (d.x * d.z),
+                            0.54627422f * (d.x * d.x - d.y * d.y)};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            acc[k][0] = acc[k][0] + l.x * b[k];
+            acc[k][1] = acc[k][1] + l.y * b[k];
+            acc[k][2] = acc[k][2] + l.z * b[k];
+            acc[k][3] = acc[k][3] + l.w * b[k];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) acc[k][ch] = acc[k][ch] + __shfl_down(acc[k][ch], off, 64);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sh[(size_t)probe * 9u + k] = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+    }
+}
+
+// The instances, (mode, triangles, threads), each for the three kinds: f(kernel, threads) for the
+// one of (mode, tris, kind). Workgroup size by placement: the global-memory instance has
 // no image to share: small workgroups, as the closest-hit query's. The staged instances share one
 // image among as many waves as their registers allow without spilling: the walks from global
 // memory with the shading state live need about 150 VGPRs (the path kernel's figure), which 16
 // waves per workgroup (128 each) would spill.
-template <bool kGather, class F>
+template <PathKind kKind, class F>
 static hipError_t with_radiance_instance(int mode, bool tris, F f) {
-    if (mode == 0 && tris) return f(&rt_radiance_kernel<0, true, 256, kGather>, 256u);
-    if (mode == 1 && tris) return f(&rt_radiance_kernel<1, true, 512, kGather>, 512u);
-    if (mode == 2 && tris) return f(&rt_radiance_kernel<2, true, 1024, kGather>, 1024u);
-    if (mode == 0 && !tris) return f(&rt_radiance_kernel<0, false, 256, kGather>, 256u);
-    if (mode == 1 && !tris) return f(&rt_radiance_kernel<1, false, 1024, kGather>, 1024u);
+    if (mode == 0 && tris) return f(&rt_radiance_kernel<0, true, 256, kKind>, 256u);
+    if (mode == 1 && tris) return f(&rt_radiance_kernel<1, true, 512, kKind>, 512u);
+    if (mode == 2 && tris) return f(&rt_radiance_kernel<2, true, 1024, kKind>, 1024u);
+    if (mode == 0 && !tris) return f(&rt_radiance_kernel<0, false, 256, kKind>, 256u);
+    if (mode == 1 && !tris) return f(&rt_radiance_kernel<1, false, 1024, kKind>, 1024u);
     return hipErrorInvalidValue;
 }
 
 // (0 for a (mode, tris) without an instance, as rt_query_threads)
 uint32_t rt_radiance_threads(int mode, bool tris) {
     uint32_t threads = 0;
-    (void)with_radiance_instance<false>(mode, tris, [&](auto, uint32_t t) { return threads = t, hipSuccess; });
+    (void)with_radiance_instance<kPathRadiance>(mode, tris, [&](auto, uint32_t t) { return threads = t, hipSuccess; });
     return threads;
 }
 
 hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
-    return with_radiance_instance<false>(
+    return with_radiance_instance<kPathRadiance>(
         mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
 }
 
 hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
-    return with_radiance_instance<true>(
+    return with_radiance_instance<kPathGather>(
         mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
+}
+
+hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return with_radiance_instance<kPathProbe>(
+        mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
+}
+
+// The launch of the instance of `kKind`: `count` items of `rays` into `radiance`.
+template <PathKind kKind>
+static hipError_t launch_path_kind(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                                   const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
+                                   unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
+                                   hipStream_t stream) {
+    if (s.blocks == 0 || count == 0) return hipSuccess;
+    return with_radiance_instance<kKind>(mode, tris, [&](auto kernel, uint32_t t) {
+        const ChunkArgs ca = chunk_args(count, counter, s, t);
+        const RadianceArgs qa{static_cast<const float4*>(rays), static_cast<float4*>(radiance),
+                              ca.count, ca.next, segments, ca.wave_chunk, ca.first_chunk, ca.claimed_from,
+                              first_sample, samples, stripes};
+        return query_launch_of(kernel, t, s.blocks, lds_bytes, stream, ka, qa);
+    });
 }
 
 // `stripes` 0: a radiance query of `count` rays. Otherwise the path kernel of a gather query:
@@ -276,15 +418,20 @@ hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t 
                               const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
                               unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
                               hipStream_t stream) {
-    if (s.blocks == 0 || count == 0) return hipSuccess;
-    auto launch = [&](auto kernel, uint32_t t) {
-        const ChunkArgs ca = chunk_args(count, counter, s, t);
-        const RadianceArgs qa{static_cast<const float4*>(rays), static_cast<float4*>(radiance),
-                              ca.count, ca.next, segments, ca.wave_chunk, ca.first_chunk, ca.claimed_from,
-                              first_sample, samples, stripes};
-        return query_launch_of(kernel, t, s.blocks, lds_bytes, stream, ka, qa);
-    };
-    return stripes ? with_radiance_instance<true>(mode, tris, launch) : with_radiance_instance<false>(mode, tris, launch);
+    return stripes ? launch_path_kind<kPathGather>(ka, mode, tris, lds_bytes, s, rays, radiance, count, counter, segments,
+                                                   first_sample, samples, stripes, stream)
+                   : launch_path_kind<kPathRadiance>(ka, mode, tris, lds_bytes, s, rays, radiance, count, counter, segments,
+                                                     first_sample, samples, 0u, stream);
+}
+
+// The path kernel of a probe query: `probes` holds rt_probe records, `count` is the launch's items
+// (probes x samples, below 2^32) and `lights` receives L_s of item t at slot t.
+hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                                 const void* probes, void* lights, uint64_t count, unsigned long long* counter,
+                                 unsigned long long* segments, uint32_t first_sample, uint32_t samples,
+                                 hipStream_t stream) {
+    return launch_path_kind<kPathProbe>(ka, mode, tris, lds_bytes, s, probes, lights, count, counter, segments,
+                                        first_sample, samples, 0u, stream);
 }
 
 // Step 4's tree over the partials of `points` points (stream-ordered after the path kernel).
@@ -294,5 +441,16 @@ hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32
     const uint32_t per_block = kResolveThreads / 64u;
     hipLaunchKernelGGL(rt_gather_resolve_kernel, dim3((points + per_block - 1u) / per_block), dim3(kResolveThreads), 0,
                        stream, static_cast<const float4*>(partials), static_cast<float4*>(radiance), points, stripes);
+    return hipGetLastError();
+}
+
+// Steps 4 and 5 over the lights of `count` probes (stream-ordered after the path kernel).
+hipError_t rt_launch_probe_resolve(const void* lights, const void* probes, void* sh, uint32_t count, uint32_t first_sample,
+                                   uint32_t samples, hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    const uint32_t per_block = kResolveThreads / 64u;
+    hipLaunchKernelGGL(rt_probe_resolve_kernel, dim3((count + per_block - 1u) / per_block), dim3(kResolveThreads), 0,
+                       stream, static_cast<const float4*>(lights), static_cast<const float4*>(probes),
+                       static_cast<float4*>(sh), count, first_sample, samples);
     return hipGetLastError();
 }

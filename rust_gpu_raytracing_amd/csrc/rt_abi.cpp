@@ -76,6 +76,13 @@ hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t 
                               hipStream_t stream);
 hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
                                     hipStream_t stream);
+hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                                 const void* probes, void* lights, uint64_t count, unsigned long long* counter,
+                                 unsigned long long* segments, uint32_t first_sample, uint32_t samples,
+                                 hipStream_t stream);
+hipError_t rt_launch_probe_resolve(const void* lights, const void* probes, void* sh, uint32_t count, uint32_t first_sample,
+                                   uint32_t samples, hipStream_t stream);
 hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
@@ -128,6 +135,7 @@ static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ra
 static_assert(sizeof(rt_gather_point) == sizeof(rt_radiance_ray), "rt_gather_point has the layout of rt_radiance_ray");
 static_assert(offsetof(rt_gather_point, stream) == 12 && offsetof(rt_gather_point, normal) == 16,
               "rt_gather_point: {position, stream}, {normal, pad} as two 16-B loads");
+static_assert(sizeof(rt_probe) == 16 && offsetof(rt_probe, stream) == 12, "rt_probe: {position, stream} as one 16-B load");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
 static_assert(sizeof(rt_sub_object_info) == sizeof(RtSubObject), "sub-object record");
@@ -203,6 +211,13 @@ constexpr uint64_t kQueryStageMinRays = 262144;
 // each (16 MiB of context-owned scratch); tuning "gather_chunk".
 constexpr uint32_t kDefaultGatherChunk = 16384;
 constexpr uint32_t kMaxGatherChunk = 1u << 20;
+// Probe queries (radiance.hip) run in launches of at most this many paths, 16 B of scratch each
+// (16 MiB of context-owned scratch), but of one whole probe at least; tuning "probe_chunk".
+constexpr uint32_t kDefaultProbeChunk = 1048576;
+constexpr uint32_t kMaxProbeChunk = 1u << 26;
+// The most samples a probe takes: one probe's scratch is then 256 MiB.
+constexpr uint32_t kMaxProbeSamples = 1u << 24;
+constexpr size_t kMaxProbeScratchBytes = (size_t)kMaxProbeSamples * 16u;
 // Feature buffers (denoise.hip): the frame's camera rays are traced in bands of this many pixels,
 // so the scratch of a band -- its rays and records, 96 B per pixel: 48 MiB -- does not grow with
 // the frame (3840x2160 would take 800 MB at once); tuning "feature_band".
@@ -458,6 +473,10 @@ struct rt_ctx {
     uint32_t gather_chunk = kDefaultGatherChunk;    // tuning "gather_chunk": points per gather launch
     void* d_gather_partials = nullptr;              // rt_gather: 64 float4 per point of a launch
     size_t gather_partials_bytes = 0;
+    uint32_t probe_chunk = kDefaultProbeChunk;      // tuning "probe_chunk": paths per probe launch
+    void* d_probe_lights = nullptr;                 // rt_probe_sh: one float4 per path of a launch
+    size_t probe_lights_bytes = 0;
+    unsigned long long* d_probe_next = nullptr;     // the chunk counters of the two launches in flight
     int q_occ_mode = -1;                        // occupancy of the last query instance
     int q_occ_kind = 0;                         // (which kernel's: QueryKind)
     bool q_occ_tris = false;
@@ -994,7 +1013,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out, ctx->d_disp_out, ctx->d_disp_meter,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
                     ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2]};
@@ -1933,17 +1952,18 @@ static int query_enter(rt_ctx* ctx) {
 // by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
 // `kind`: the kernel the view is for -- rt_query_kernel, rt_occlusion_kernel (occlusion.hip) or
 // rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
-// its gather instance (points x samples).
-enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2, kQueryGather = 3 };
+// its gather instance (points x samples) or its probe instance (probes x samples).
+enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2, kQueryGather = 3, kQueryProbe = 4 };
 
 // Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
 static const struct {
     uint32_t (*threads)(int mode, bool tris);
     hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-} kQueryKernels[4] = {{rt_query_threads, rt_query_occupancy},
+} kQueryKernels[5] = {{rt_query_threads, rt_query_occupancy},
                       {rt_occlusion_threads, rt_occlusion_occupancy},
                       {rt_radiance_threads, rt_radiance_occupancy},
-                      {rt_radiance_threads, rt_gather_occupancy}};
+                      {rt_radiance_threads, rt_gather_occupancy},
+                      {rt_radiance_threads, rt_probe_occupancy}};
 
 struct QueryLaunch {
     KernelArgs ka{};
@@ -2029,11 +2049,12 @@ static int query_buffers(rt_ctx* ctx, size_t n) {
     return RT_OK;
 }
 
-// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather): the `count` records
+// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather, rt_probe_sh): the `count` records
 // of `in_bytes` each at host pointer `in` go through the pinned and the device scratch in chunks of
 // "query_chunk"; run(device in, device out, n) answers a chunk, and `out_bytes` per record come
 // back to `out`. Both scratch buffers hold the inputs at their base and the results at capacity x
-// 32 bytes (where the records of a closest-hit chunk go). With `count_segments` the context's
+// 32 bytes (where the records of a closest-hit chunk go); a call whose results exceed 32 bytes per
+// record (rt_probe_sh: 144) sizes both by that many records more. With `count_segments` the context's
 // segment counter is zeroed first and read back after the last chunk, into the pinned bytes after
 // a chunk's results, for `segments` (which may be null).
 extern "C++" template <class Run>  // (a template inside the extern "C" block of the entry points)
@@ -2043,7 +2064,7 @@ static int staged_query(rt_ctx* ctx, const void* in, size_t in_bytes, void* out,
     if (rc) return rc;
     if (count_segments && !ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
     const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
-    if ((rc = query_buffers(ctx, chunk))) return rc;
+    if ((rc = query_buffers(ctx, chunk * ((out_bytes + 31u) / 32u)))) return rc;
     unsigned char* d_in = static_cast<unsigned char*>(ctx->d_query_buf);
     unsigned char* d_out = d_in + ctx->query_buf_rays * sizeof(rt_query_ray);
     unsigned char* h_in = static_cast<unsigned char*>(ctx->query_pinned);
@@ -2624,6 +2645,108 @@ int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance, uint6
                         });
 }
 
+// ---- probe queries (radiance.hip, kPathProbe) ---------------------------------------------------
+//
+// Per probe, the second-order spherical-harmonic projection of the light of `samples` paths that
+// leave the point in uniform directions (the contract in include/rt_abi.h). The path kernel is the
+// radiance kernel's probe instance over (probe, sample) items, which stores every path's light;
+// rt_probe_resolve_kernel projects and reduces each probe's lights.
+
+// Bakes `count` probes at device pointer `probes` into `sh`, stream-ordered on the primary stream,
+// in launches of whole probes, max(1, "probe_chunk" / samples) of them, two of them in flight (the
+// primary stream is ordered after both on return); the counted segments are added to the device
+// counter `segments` (null: not counted).
+static int run_probe_sh(rt_ctx* ctx, const void* probes, void* sh, uint64_t count, uint32_t bounces,
+                        uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
+    if (count == 0) return RT_OK;
+    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
+        RT_HIP(ctx, hipMemsetAsync(sh, 0, (size_t)count * 144u, ctx->stream));
+        return RT_OK;
+    }
+    QueryLaunch q;
+    bool answered;
+    int rc = path_query_scene(ctx, nullptr, count, bounces, samples, kQueryProbe, q, &answered);
+    if (rc) return rc;
+    // whole probes per launch: at most max("probe_chunk", samples) <= 2^26 items, 16 B each
+    const uint64_t chunk = std::min<uint64_t>(count, std::max<uint32_t>(1u, ctx->probe_chunk / samples));
+    const size_t bytes = (size_t)chunk * samples * 16u;
+    // A call of several launches alternates them between the primary and the auxiliary stream, each
+    // with its own half of the scratch and its own chunk counter: a launch of a million paths is
+    // mostly fill and drain (four items per resident lane), and the next launch's workgroups take
+    // the CUs the draining one gives up. Not where that would take the scratch beyond its cap.
+    const bool overlap = count > chunk && 2u * bytes <= kMaxProbeScratchBytes;
+    if ((rc = grow_buffer(ctx, &ctx->d_probe_lights, &ctx->probe_lights_bytes, overlap ? 2u * bytes : bytes))) return rc;
+    if (overlap) {
+        if (!ctx->d_probe_next && (rc = dev_alloc(ctx, &ctx->d_probe_next, 2))) return rc;
+        RT_HIP(ctx, hipEventRecord(ctx->ev_primary, ctx->stream));  // the probes are there, the scratch is free
+        RT_HIP(ctx, hipStreamWaitEvent(ctx->aux_stream, ctx->ev_primary, 0));
+    }
+    // orders the primary stream after the auxiliary one again (on every way out)
+    auto join = [&]() -> hipError_t {
+        if (!overlap) return hipSuccess;
+        const hipError_t e = hipEventRecord(ctx->ev_aux_done, ctx->aux_stream);
+        if (e != hipSuccess) return e;
+        ctx->aux_outstanding = true;
+        return join_aux(ctx);
+    };
+    uint32_t group = 0;
+    for (uint64_t done = 0; done < count; ++group) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
+        const uint64_t items = (uint64_t)n * samples;
+        const rtq::QuerySchedule s = rtq::query_schedule(items, q.waves_per_block, q.resident,
+                                                         rtq::kRadianceFirstChunkMax, rtq::kRadianceChunkMax);
+        const uint32_t slot = overlap ? group & 1u : 0u;
+        hipStream_t S = slot ? ctx->aux_stream : ctx->stream;
+        unsigned long long* next = overlap ? ctx->d_probe_next + slot : ctx->d_query_next;
+        unsigned char* lights = static_cast<unsigned char*>(ctx->d_probe_lights) + slot * bytes;
+        const unsigned char* records = static_cast<const unsigned char*>(probes) + done * sizeof(rt_probe);
+        hipError_t e = hipMemsetAsync(next, 0, sizeof(unsigned long long), S);
+        if (e == hipSuccess)
+            e = rt_launch_probe_paths(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, records, lights, items, next, segments,
+                                      first_sample, samples, S);
+        if (e == hipSuccess)
+            e = rt_launch_probe_resolve(lights, records, static_cast<unsigned char*>(sh) + done * 144u, n, first_sample,
+                                        samples, S);
+        if (e != hipSuccess) {
+            (void)join();
+            return hip_fail(ctx, "rt_probe_sh launch", e);
+        }
+        done += n;
+    }
+    RT_HIP(ctx, join());
+    return RT_OK;
+}
+
+int rt_probe_sh_device(rt_ctx* ctx, const void* probes_device, void* sh_device, uint64_t count, uint32_t bounces,
+                       uint32_t first_sample, uint32_t samples, void* segments_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_probe_sh_device: samples is 0");
+    if (samples > kMaxProbeSamples) return fail(ctx, RT_E_INVALID, "rt_probe_sh_device: samples above 16777216");
+    if (count == 0) return RT_OK;
+    int rc = check_device_ptrs(ctx, "rt_probe_sh_device", {{probes_device, "probes", 16, false},
+                                                           {sh_device, "sh", 16, false},
+                                                           {segments_device, "segments", 8, true}});
+    if (rc || (rc = query_enter(ctx))) return rc;
+    return run_probe_sh(ctx, probes_device, sh_device, count, bounces, first_sample, samples,
+                        static_cast<unsigned long long*>(segments_device));
+}
+
+int rt_probe_sh(rt_ctx* ctx, const rt_probe* probes, float* sh, uint64_t count, uint32_t bounces, uint32_t first_sample,
+                uint32_t samples, uint64_t* segments) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_probe_sh: samples is 0");
+    if (samples > kMaxProbeSamples) return fail(ctx, RT_E_INVALID, "rt_probe_sh: samples above 16777216");
+    if (count == 0) {
+        if (segments) *segments = 0;
+        return RT_OK;
+    }
+    if (!probes || !sh) return fail(ctx, RT_E_INVALID, "rt_probe_sh: probes or sh is NULL");
+    return staged_query(ctx, probes, sizeof(rt_probe), sh, 144, count, true, segments,
+                        [&](const void* d_probes, void* d_sh, uint64_t n) {
+                            return run_probe_sh(ctx, d_probes, d_sh, n, bounces, first_sample, samples, ctx->d_radiance_segs);
+                        });
+}
+
 int rt_read_output(rt_ctx* ctx, uint32_t* out) {
     RT_ENTER(ctx);
     if (!out) return fail(ctx, RT_E_INVALID, "out is NULL");
@@ -2917,6 +3040,8 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         if ((rc = range(1, (int32_t)kMaxQueryChunk)) == RT_OK) ctx->query_chunk = (uint32_t)v;
     } else if (k == "gather_chunk") {
         if ((rc = range(1, (int32_t)kMaxGatherChunk)) == RT_OK) ctx->gather_chunk = (uint32_t)v;
+    } else if (k == "probe_chunk") {
+        if ((rc = range(1, (int32_t)kMaxProbeChunk)) == RT_OK) ctx->probe_chunk = (uint32_t)v;
     } else if (k == "query_lds_mode") {
         if ((rc = range(-1, 2)) == RT_OK) ctx->query_lds_mode = v;
     } else if (k == "feature_band") {

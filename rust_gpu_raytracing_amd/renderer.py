@@ -522,6 +522,69 @@ class Renderer:
         cur.wait_stream(mine)
         return (out, int(segments.item())) if return_segments else out
 
+    # ------------------------------------------------------------------ probe queries
+    def probe_sh(self, positions, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,
+                 samples: int = 256, return_segments: bool = False):
+        """The light arriving at each point in free space, as second-order spherical harmonics
+        (rt_probe_sh): per probe and colour channel, the nine sums of L * b_k over ``samples``
+        paths that leave the point in uniform directions drawn on the device. The sums are the
+        contract's stripe-and-tree reduction (include/rt_abi.h), bit-exact whatever the schedule.
+        Multiply by 4 pi / ``samples`` for the radiance coefficients (``sh.radiance`` and
+        ``sh.irradiance`` do); nothing is clamped. Against the scene as it is now, without
+        touching anything a render reads.
+
+        ``positions``: an (n, 3) float32 array, with ``streams`` an (n,) uint32 array of RNG
+        streams (default: 1 + the probe's position in the batch: stream 0 draws the same sample
+        every time), or a ``buffers.PROBE`` array. Returns an (n, 9, 4) float32 array, and with
+        ``return_segments`` the call's counted ray segments. A CUDA torch tensor of shape (n, 4)
+        float32 (rt_probe records: the stream's bits in column 3) goes through
+        rt_probe_sh_device instead -- no host round trip, stream-ordered on the context's stream
+        -- and returns a CUDA (n, 9, 4) float32 tensor."""
+        if not isinstance(positions, np.ndarray) and hasattr(positions, "is_cuda"):
+            if streams is not None:
+                raise ValueError("device probes carry their stream in column 3")
+            return self._probe_sh_device(positions, bounces, first_sample, samples, return_segments)
+        probes = np.asarray(positions)
+        if probes.dtype == B.PROBE:
+            if streams is not None:
+                raise ValueError("PROBE records carry their own stream")
+        else:
+            r = np.ascontiguousarray(probes, np.float32)
+            if r.ndim != 2 or r.shape[1] != 3:
+                raise ValueError("positions must be (n, 3) float32 or a PROBE array")
+            probes = np.zeros(r.shape[0], B.PROBE)
+            probes["position"] = r
+            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
+            if s.shape != (r.shape[0],):
+                raise ValueError("streams must be an (n,) array")
+            probes["stream"] = s
+        probes = np.ascontiguousarray(probes.reshape(-1))
+        out = np.zeros((probes.shape[0], 9, 4), np.float32)
+        segments = ctypes.c_uint64(0)
+        self._call("rt_probe_sh", N.ptr(probes), N.ptr(out), probes.shape[0], int(bounces), int(first_sample),
+                   int(samples), ctypes.byref(segments))
+        return (out, segments.value) if return_segments else out
+
+    def _probe_sh_device(self, probes, bounces, first_sample, samples, return_segments):
+        import torch
+
+        if not probes.is_cuda or probes.dtype != torch.float32 or probes.dim() != 2 or probes.shape[1] != 4:
+            raise ValueError("device probes must be a CUDA float32 tensor of shape (n, 4)")
+        if probes.device.index != self.device:
+            raise ValueError("device probes must live on the renderer's device")
+        probes = probes.contiguous()
+        out = torch.empty((probes.shape[0], 9, 4), dtype=torch.float32, device=probes.device)
+        segments = torch.zeros(1, dtype=torch.int64, device=probes.device) if return_segments else None
+        # the stream handshake of _trace_rays_device
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=probes.device)
+        cur = torch.cuda.current_stream(probes.device)
+        mine.wait_stream(cur)
+        self._call("rt_probe_sh_device", ctypes.c_void_p(probes.data_ptr() if probes.shape[0] else None),
+                   ctypes.c_void_p(out.data_ptr() if probes.shape[0] else None), probes.shape[0], int(bounces),
+                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
+        cur.wait_stream(mine)
+        return (out, int(segments.item())) if return_segments else out
+
     # ------------------------------------------------------------------ feature buffers & denoiser
     def compute_features(self) -> None:
         """rt_compute_features: the first-hit feature planes, recomputed only after a camera or

@@ -1,7 +1,7 @@
 """Throughput of the ray-query kernel (rt_trace_rays_device) and its placement crossover.
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
-                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather]
+                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather] [--probe]
                                    [--out profiles/query_bench.jsonl]
 
 Rays: the configuration's width x height camera rays (coherent: neighbouring rays are
@@ -46,6 +46,14 @@ checks that all trace equal segments and that the contract's tree over the by-ha
 the gather bit for bit. Next to them: rt_radiance_device on the points' first records at samples
 = --samples, the shape the gather call replaces (one direction per point, its samples back to
 back on one lane). Device events on the context's stream; median, minimum and maximum over --rounds.
+--probe: the probe query (rt_probe_sh_device) against the same paths done by hand, in one process
+(DESIGN.md §5.4i). --points probes (4,096) are the first hits of the camera rays moved 0.25 along the
+normal, streams 1..n, at --samples samples (1,024). The yardstick is the parent's code, as for
+--gather: the records of the same paths made on the host (tools/gather_records.c with zero normals,
+folded streams) and traced by one rt_radiance_device call with samples = 1 and first_sample = 1, in
+both record orders. Each round checks that all trace equal segments and that steps 4 and 5 of the
+probe contract over the by-hand results (torch's f32 multiply and add, one operation each) equal
+the probe call bit for bit.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -381,6 +389,137 @@ def gather_bench(r, args, scene, bounces, dev, emit):
          records_host_ms=round(min(host_ms.values()), 1), records_mb=round(records.nbytes / 2 ** 20, 1), build=r._lib.rt_build_hash().decode(), **row)
 
 
+def probe_bench(r, args, scene, bounces, dev, emit):
+    """The --probe series (module docstring)."""
+    import statistics
+
+    import torch
+
+    n, samples, first = args.points, args.samples, 1
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+    P = ctypes.c_void_p
+
+    # the probes: first hits of the camera rays, spread evenly over the image, moved into free space
+    q = camera_query_rays(scene)
+    q_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    hits_t = torch.empty((q.shape[0], 16), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    r._call("rt_trace_rays_device", P(q_t.data_ptr()), P(hits_t.data_ptr()), q.shape[0])
+    r.synchronize()
+    h = hits_t.cpu().numpy().view(B.HIT).reshape(-1)
+    hit = np.nonzero(h["kind"] != B.HIT_MISS)[0]
+    assert hit.shape[0] >= n, (hit.shape[0], n)
+    pick = hit[np.linspace(0, hit.shape[0] - 1, n).astype(np.int64)]
+    probes = np.zeros(n, B.PROBE)
+    probes["position"] = h["position"][pick] + h["normal"][pick] * np.float32(0.25)
+    probes["stream"] = 1 + np.arange(n, dtype=np.uint32)
+    points = np.zeros(n, B.GATHER_POINT)  # the same paths as gather points: normal (0, 0, 0)
+    points["position"], points["stream"] = probes["position"], probes["stream"]
+    del q_t, hits_t
+
+    helper = build_gather_records()
+    rec_t, host_ms = {}, {}
+    for order, point_major in (("sample_major", 0), ("point_major", 1)):
+        t0 = time.perf_counter()
+        records = np.zeros((samples * n, 8), np.float32)
+        helper.gather_records(points.ctypes.data, n, first, samples, point_major, records.ctypes.data)
+        host_ms[order] = (time.perf_counter() - t0) * 1e3
+        # a draw of -0 (rho = -0 at r = 1: about one in 2^24 draws) is +0 in these records, 0 + g, and
+        # -0 in the probe's direction; the jitter's add and step 5's +0.0f start absorb the sign, and
+        # the bit comparison of every round is the check
+        zero_draws = int((records[:, 4:7] == 0).sum())
+        rec_t[order] = torch.from_numpy(records).to(dev)
+    probes_t = torch.from_numpy(probes.view(np.float32).reshape(-1, 4)).to(dev)
+    hand_t = torch.empty((samples * n, 4), dtype=torch.float32, device=dev)
+    sh_t = torch.empty((n, 9, 4), dtype=torch.float32, device=dev)
+    seg_t = torch.zeros(3, dtype=torch.int64, device=dev)  # by hand in both orders, the probe call
+    torch.cuda.synchronize()
+    seg = [P(seg_t.data_ptr() + 8 * i) for i in range(3)]
+
+    def by_hand(order, counter):
+        r._call("rt_radiance_device", P(rec_t[order].data_ptr()), P(hand_t.data_ptr()), n * samples, bounces, 1, 1,
+                seg[counter])
+
+    def probe():
+        r._call("rt_probe_sh_device", P(probes_t.data_ptr()), P(sh_t.data_ptr()), n, bounces, first, samples, seg[2])
+
+    def basis(d):  # step 4 on (..., 3): each torch operation is one f32 operation
+        x, y, z = d[..., 0], d[..., 1], d[..., 2]
+        c1, c2 = 0.48860251, 1.09254843
+        return torch.stack([torch.full_like(x, 0.28209479), c1 * y, c1 * z, c1 * x, c2 * (x * y), c2 * (y * z),
+                            0.31539157 * (3.0 * (z * z) - 1.0), c2 * (x * z), 0.54627422 * (x * x - y * y)], dim=-1)
+
+    def tree(terms):  # step 5 on (samples, n, 4)
+        p = torch.zeros((64, n, 4), dtype=torch.float32, device=dev)
+        for k in range(0, samples, 64):
+            m = min(64, samples - k)
+            p[:m] = p[:m] + terms[k:k + m]
+        off = 32
+        while off:
+            p[:off] = p[:off] + p[off:2 * off]
+            off //= 2
+        return p[0]
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        fn()
+        t1.record(stream)
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    def hand_projection(order):  # steps 4 and 5 over what the by-hand call just wrote
+        r.synchronize()
+        rec = rec_t[order]
+        if order == "sample_major":
+            lights, dirs = hand_t.view(samples, n, 4), rec.view(samples, n, 8)[..., 4:7]
+        else:
+            lights, dirs = hand_t.view(n, samples, 4).permute(1, 0, 2), rec.view(n, samples, 8).permute(1, 0, 2)[..., 4:7]
+        b = basis(dirs)
+        ok = True
+        for k in range(9):
+            want = tree(lights * b[..., k:k + 1])
+            ok = ok and bool(torch.equal(want.view(torch.int32), sh_t[:, k].contiguous().view(torch.int32)))
+        torch.cuda.synchronize()
+        return ok
+
+    for fn in (lambda: by_hand("sample_major", 0), lambda: by_hand("point_major", 1), probe):
+        fn()  # warm-up of every shape and placement
+    r.synchronize()
+    ms = {"by_hand_sample_major": [], "by_hand_point_major": [], "probe": []}
+    segments, same = [], []
+    for _ in range(args.rounds):
+        seg_t.zero_()
+        sh_t.zero_()
+        torch.cuda.synchronize()
+        ms["probe"].append(timed(probe))
+        assert bool(sh_t.view(torch.int32).any())
+        ok = []
+        for counter, order in enumerate(("sample_major", "point_major")):
+            hand_t.zero_()
+            torch.cuda.synchronize()
+            ms["by_hand_" + order].append(timed(lambda: by_hand(order, counter)))
+            ok.append(hand_projection(order))
+        r.synchronize()
+        counted = [int(v) for v in seg_t.cpu().numpy()]
+        assert counted[0] == counted[1] == counted[2], counted
+        assert all(ok), "steps 4 and 5 over the by-hand results differ from the probe call"
+        segments.append(counted)
+        same.append(all(ok))
+    med = statistics.median
+    ms["by_hand"] = min(ms["by_hand_sample_major"], ms["by_hand_point_major"], key=med)  # the faster order is the yardstick
+    row = {k + "_ms": round(med(v), 3) for k, v in ms.items()}
+    row.update({k + "_ms_min": round(min(v), 3) for k, v in ms.items()})
+    row.update({k + "_ms_max": round(max(v), 3) for k, v in ms.items()})
+    emit(kind="probe", bounces=bounces, probes=n, samples=samples, rounds=args.rounds, paths=n * samples,
+         segments_per_path=round(segments[0][2] / (n * samples), 4), segments_equal=True, sh_bit_identical=all(same),
+         probe_over_by_hand=round(med(ms["probe"]) / med(ms["by_hand"]), 4),
+         probe_mray_s=round(segments[0][2] / med(ms["probe"]) / 1e3, 1),
+         by_hand_mray_s=round(segments[0][0] / med(ms["by_hand"]) / 1e3, 1),
+         records_host_ms=round(min(host_ms.values()), 1), records_mb=round(records.nbytes / 2 ** 20, 1),
+         zero_draws=zero_draws, build=r._lib.rt_build_hash().decode(), **row)
+
+
 def main():
     import torch
 
@@ -394,9 +533,11 @@ def main():
     ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
     ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
     ap.add_argument("--gather", action="store_true", help="the gather query against the same paths done by hand")
-    ap.add_argument("--points", type=int, default=4096, help="--gather: surface points")
-    ap.add_argument("--samples", type=int, default=1024, help="--gather: samples per point")
-    ap.add_argument("--bounces", type=int, default=None, help="--radiance, --gather: bounce limit (default: the configuration's)")
+    ap.add_argument("--probe", action="store_true", help="the probe query against the same paths done by hand")
+    ap.add_argument("--points", type=int, default=4096, help="--gather: surface points; --probe: probes")
+    ap.add_argument("--samples", type=int, default=1024, help="--gather, --probe: samples per point")
+    ap.add_argument("--bounces", type=int, default=None,
+                    help="--radiance, --gather, --probe: bounce limit (default: the configuration's)")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="--radiance: untimed work before the rounds")
     ap.add_argument("--rounds", type=int, default=7, help="--occluded, --radiance: rounds the series alternate over")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
@@ -427,7 +568,9 @@ def main():
     call = "rt_occluded_device" if args.occluded else "rt_trace_rays_device"
     tuning = {k: int(v) for k, v in (kv.split("=", 1) for kv in args.tune)}
     with Renderer(scene, tuning=tuning) as r:
-        if args.gather:
+        if args.probe:
+            probe_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
+        elif args.gather:
             gather_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
         elif args.radiance:
             radiance_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
