@@ -55,7 +55,8 @@ extern "C" {
  * 12, additive: gather queries (rt_gather, rt_gather_device, rt_gather_point);
  * 12, additive: display transform (rt_display, rt_read_display, rt_copy_display_to_device,
  * rt_display_state, rt_display_reset, rt_display_default_params, rt_display_params);
- * 12, additive: probe queries (rt_probe_sh, rt_probe_sh_device, rt_probe). */
+ * 12, additive: probe queries (rt_probe_sh, rt_probe_sh_device, rt_probe);
+ * 12, additive: ambient queries (rt_ambient, rt_ambient_device, rt_ambient_point). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -700,6 +701,93 @@ RT_API int rt_probe_sh_device(rt_ctx* ctx, const void* probes_device, void* sh_d
                               uint32_t bounces, uint32_t first_sample, uint32_t samples,
                               void* segments_device /* may be NULL; one u64, added to */);
 
+/* ---- ambient queries (ABI 12, additive: ambient queries) ---------------------
+ *
+ * "Which part of the hemisphere over this surface point is open?": per point, the number of
+ * `samples` directions through the gather's lobe that nothing blocks within t_max (ambient
+ * occlusion, or sky visibility for an unbounded t_max) and the sum of those directions (the bent
+ * normal). Occlusion baking for lightmap texels and vertices: the any-hit counterpart of
+ * rt_gather. The directions are drawn on the device, every sample is one any-hit search of
+ * rt_occluded, the samples of a point are spread over the lanes of the device, and the reduction
+ * order is stated, so every value is bit-exact and independent of placement and schedule. The
+ * bent normal is also the direction to look an rt_probe_sh probe up with. */
+
+/* {position, stream}, {normal, t_max}: the layout of rt_gather_point with the distance bound in the
+ * place of _pad1 (where rt_occlusion_ray keeps it). 32 bytes. */
+typedef struct rt_ambient_point {
+    float position[3];
+    uint32_t stream;  /* as in rt_gather_point; use streams >= 1 */
+    float normal[3];  /* used as given: not normalised */
+    float t_max;      /* the AO radius, in world units (the directions are unit length) */
+} rt_ambient_point;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_ambient_point) == 32, "rt_ambient_point is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_ambient_point) == 32, "rt_ambient_point is 32 bytes");
+#endif
+
+/* Writes four floats per point, in order: bent.x, bent.y, bent.z, open; nothing outside
+ * [0, 4 * count) is written.
+ *
+ * THE AMBIENT CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+ * written order, with no contraction. For point i with record (x, stream, n, t_max):
+ *  1. Sample index and origin: step 1 of the gather contract. For s = 0 .. samples-1,
+ *     u = first_sample + s (u32, wrapping). o = x + n * 0.0001f per component: one multiply and
+ *     one add.
+ *  2. Direction: step 2 of the gather contract. dseed = (stream * u * 326624u) ^ 0x9E3779B9u
+ *     (u32, wrapping). gx, gy, gz = normal_distribution(&dseed) three times, in that order.
+ *     dir = normalize(n + (gx, gy, gz)) with normalize(v) = v * (1.0f / sqrt(dot(v, v))) and
+ *     dot(v, v) = (x*x + y*y) + z*z. n is used as given and is not normalised. There is no
+ *     jitter: dir is the ray's direction as is.
+ *  3. Visibility. B_s is the byte rt_occluded defines for the record (o, dir, t_max): 1 iff a
+ *     primitive is accepted at a non-NaN distance t < t_max (strictly); t_max <= 0 or NaN
+ *     gives 0. V_s = 1 - B_s.
+ *  4. Term. T_s = (dir.x, dir.y, dir.z, 1.0f) where V_s == 1, and
+ *     T_s = (+0.0f, +0.0f, +0.0f, +0.0f) where V_s == 0.
+ *  5. Reduction: step 4 of the gather contract on T_s. P_j (j = 0 .. 63) starts at +0.0f on all
+ *     four channels. For s ascending, P_{s mod 64} = P_{s mod 64} + T_s. Then, for
+ *     off = 32, 16, 8, 4, 2, 1: P_j = P_j + P_{j+off} for every j < off. out[i] = P_0. Lanes
+ *     that got no sample take part with +0.0f.
+ * End of the ambient contract.
+ *
+ * Consequences:
+ *  - `open` (channel w) is an integer-valued float, exact whatever the order of addition, because
+ *    samples <= 16777216. Above that the call is RT_E_INVALID.
+ *  - samples == 0 is RT_E_INVALID (whatever `count` is).
+ *  - Ambient occlusion is open / samples. The bent normal is `bent`, normalised by the caller;
+ *    `bent` is all +0.0f when open == 0.
+ *  - t_max = +inf or 3.4028235e38f asks for sky visibility: any hit at all, as rt_occluded
+ *    defines it.
+ *  - t_max <= 0 or NaN gives open == samples (and `bent` the reduction of every direction).
+ *  - Stream 0 makes the seed constant, so it draws the same direction every time, and a draw of
+ *    exactly 0 makes rho infinite (the result is then unspecified): the caveats of rt_gather.
+ *  - The exactness domain and the termination argument are those of the occlusion queries
+ *    (position and normal are such that o and dir are in it). A lane runs at most
+ *    ceil(samples / 64) searches per (point, stripe) it takes.
+ *
+ * Scene visibility and side effects are those of rt_occluded: the query sees the scene as of
+ * the call; materials, textures and the environment do not matter; queued frames stay queued and
+ * nothing a render observes changes. The result does not depend on the brute-force mode, on any
+ * rt_set_tuning key or on triangle pruning modes 0 and 1. It works on rank contexts
+ * (world_size > 1).
+ *
+ * Both entry points run in launches of at most tuning "gather_chunk" points, with the partials
+ * P_j in the buffer rt_gather uses (1 KB per point of a launch).
+ * rt_ambient: host pointers, synchronous. Staged through the pinned buffer of rt_trace_rays in
+ * chunks of tuning "query_chunk" points (32 bytes in, 16 bytes out per point).
+ * rt_ambient_device: device pointers on the context's device; points and out 16-byte aligned;
+ * stream-ordered on rt_stream(ctx), no host copy, asynchronous. RT_E_INVALID when either is not
+ * device memory of the context's device, as for rt_gather_device.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries; by default calls
+ * of fewer than 262144 walks (count * samples) read the scene from global memory.
+ * count == 0 returns RT_OK and launches nothing; a NULL points or out pointer with count > 0 is
+ * RT_E_INVALID. */
+RT_API int rt_ambient(rt_ctx* ctx, const rt_ambient_point* points, float* out /* 4 floats per point */,
+                      uint64_t count, uint32_t first_sample, uint32_t samples);
+RT_API int rt_ambient_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count,
+                             uint32_t first_sample, uint32_t samples);
+
 /* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
  *
  * What an interactive host shows right after the camera or the scene moved: the reference resets
@@ -1170,10 +1258,12 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   "tri_octants" 1|0, "tri_qnodes" 1|0, "coop_leaves" 1|0, "stage_subs" 1|0,
  *   "primary_pass" -1|0|1 (-1: by scene), "primary_threads" 256|64|128|512|1024,
  *   "primary_waves" 8|0, "primary_tile_major" 1|0;
- *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays, rt_occluded and rt_radiance),
+ *   ray queries: "query_chunk" 65536 (1..2^24: rays per staged chunk of rt_trace_rays, rt_occluded and rt_radiance,
+ *   points of rt_gather and rt_ambient, probes of rt_probe_sh),
  *   "query_lds_mode" -1|0|1|2 (-1: mode 0 below 262144 rays, else the dispatch's placement;
  *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does),
- *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather and rt_gather_device, 1 KB of partials each),
+ *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather, rt_gather_device, rt_ambient and
+ *   rt_ambient_device, 1 KB of partials each),
  *   "probe_chunk" 1048576 (1..2^26: paths per launch of rt_probe_sh and rt_probe_sh_device, 16 B of scratch each;
  *   a launch covers whole probes, max(1, probe_chunk / samples) of them);
  *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),

@@ -98,6 +98,11 @@ class rt_gather_point(ctypes.Structure):
                 ("normal", ctypes.c_float * 3), ("_pad1", ctypes.c_float)]
 
 
+class rt_ambient_point(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_float * 3), ("stream", ctypes.c_uint32),
+                ("normal", ctypes.c_float * 3), ("t_max", ctypes.c_float)]
+
+
 class rt_probe(ctypes.Structure):
     _fields_ = [("position", ctypes.c_float * 3), ("stream", ctypes.c_uint32)]
 
@@ -134,6 +139,7 @@ assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
 assert ctypes.sizeof(rt_radiance_ray) == 32
 assert ctypes.sizeof(rt_gather_point) == 32 and rt_gather_point.stream.offset == 12 and rt_gather_point.normal.offset == 16
+assert ctypes.sizeof(rt_ambient_point) == 32 and rt_ambient_point.stream.offset == 12 and rt_ambient_point.t_max.offset == 28
 assert ctypes.sizeof(rt_probe) == 16 and rt_probe.stream.offset == 12
 assert ctypes.sizeof(rt_ray_camera) == 16
 
@@ -180,6 +186,8 @@ SIGNATURES = {
     "rt_gather_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_probe_sh": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_probe_sh_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
+    "rt_ambient": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32]),
+    "rt_ambient_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32]),
     "rt_denoise_default_params":(ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
     "rt_compute_features": (ctypes.c_int, [_P]),
     "rt_read_features": (ctypes.c_int, [_P, _P, _P]),

@@ -120,6 +120,9 @@ RADIANCE_RAY = np.dtype([("origin", "<f4", 3), ("stream", "<u4"), ("direction", 
 # rt_gather_point -- gather queries (rt_gather): the layout of RADIANCE_RAY with a surface point and
 # its normal; the result is four float32 per point
 GATHER_POINT = np.dtype([("position", "<f4", 3), ("stream", "<u4"), ("normal", "<f4", 3), ("_pad1", "<f4")])
+# rt_ambient_point -- ambient queries (rt_ambient): a GATHER_POINT with the distance bound in the place
+# of _pad1; the result is four float32 per point (the bent normal's sum, then the open count)
+AMBIENT_POINT = np.dtype([("position", "<f4", 3), ("stream", "<u4"), ("normal", "<f4", 3), ("t_max", "<f4")])
 # rt_probe -- probe queries (rt_probe_sh): a point in free space and its RNG stream; the result is
 # nine float32 rgba coefficients per probe
 PROBE = np.dtype([("position", "<f4", 3), ("stream", "<u4")])
@@ -138,7 +141,7 @@ DISPLAY_PARAMS = np.dtype([("source", "<u4"), ("tone_operator", "<u4"), ("encode
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
-    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (PROBE, 16), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
+    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (AMBIENT_POINT, 32), (PROBE, 16), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
     (DISPLAY_PARAMS, 48),
 ):
     assert _dt.itemsize == _size, (_dt, _size)

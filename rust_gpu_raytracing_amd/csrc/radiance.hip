@@ -184,11 +184,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
             const float4 r0 = qa.rays[2ull * (ray >> 6)], r1 = qa.rays[2ull * (ray >> 6) + 1ull];
             const f3 n = mk(r1.x, r1.y, r1.z);
             const uint32_t stream = __float_as_uint(r0.w), u = qa.first_sample + sample;
-            uint32_t dseed = (stream * u * 326624u) ^ 0x9E3779B9u;
-            const float gx = normal01(dseed);
-            const float gy = normal01(dseed);
-            const float gz = normal01(dseed);
-            start_sample_at(mk(r0.x, r0.y, r0.z) + n * 0.0001f, stream, u, normalize(n + mk(gx, gy, gz)), p);
+            start_sample_at(mk(r0.x, r0.y, r0.z) + n * 0.0001f, stream, u, gather_direction(n, stream, u), p);
         } else {
             const float4 r0 = qa.rays[2ull * ray], r1 = qa.rays[2ull * ray + 1ull];
             start_sample_at(mk(r0.x, r0.y, r0.z), __float_as_uint(r0.w), qa.first_sample + sample,

@@ -55,7 +55,7 @@ hipError_t rt_launch_brute_wf(const KernelArgs& ka, bool tris, bool scalar_strea
                               hipStream_t stream);
 size_t rt_brute_wf_tile_bytes(bool scalar_stream);
 uint32_t rt_brute_wf_chunk();
-// the query kernels (query.hip, occlusion.hip, radiance.hip): per kernel the workgroup size of a
+// the query kernels (query.hip, occlusion.hip, radiance.hip, ambient.hip): per kernel the workgroup size of a
 // placement, the resident workgroups per CU, and the launch on a schedule of rt_query_schedule.h
 uint32_t rt_query_threads(int mode, bool tris);
 hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
@@ -76,6 +76,11 @@ hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t 
                               hipStream_t stream);
 hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
                                     hipStream_t stream);
+uint32_t rt_ambient_threads(int mode, bool tris);
+hipError_t rt_ambient_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                             const void* points, void* partials, uint64_t count, unsigned long long* counter,
+                             uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
 hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
 hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                                  const void* probes, void* lights, uint64_t count, unsigned long long* counter,
@@ -135,6 +140,10 @@ static_assert(offsetof(rt_radiance_ray, stream) == 12 && offsetof(rt_radiance_ra
 static_assert(sizeof(rt_gather_point) == sizeof(rt_radiance_ray), "rt_gather_point has the layout of rt_radiance_ray");
 static_assert(offsetof(rt_gather_point, stream) == 12 && offsetof(rt_gather_point, normal) == 16,
               "rt_gather_point: {position, stream}, {normal, pad} as two 16-B loads");
+static_assert(sizeof(rt_ambient_point) == sizeof(rt_gather_point), "rt_ambient_point is an rt_gather_point with t_max for _pad1");
+static_assert(offsetof(rt_ambient_point, stream) == 12 && offsetof(rt_ambient_point, normal) == 16 &&
+                  offsetof(rt_ambient_point, t_max) == 28,
+              "rt_ambient_point: {position, stream}, {normal, t_max} as two 16-B loads");
 static_assert(sizeof(rt_probe) == 16 && offsetof(rt_probe, stream) == 12, "rt_probe: {position, stream} as one 16-B load");
 static_assert(sizeof(rt_scene_material) == sizeof(RtMaterial), "material record");
 static_assert(sizeof(rt_object_info) == sizeof(RtObject), "object record");
@@ -1952,18 +1961,27 @@ static int query_enter(rt_ctx* ctx) {
 // by tuning "query_lds_mode", or by default at mode 0 for batches too small to repay staging.
 // `kind`: the kernel the view is for -- rt_query_kernel, rt_occlusion_kernel (occlusion.hip) or
 // rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
-// its gather instance (points x samples) or its probe instance (probes x samples).
-enum QueryKind { kQueryClosest = 0, kQueryAnyHit = 1, kQueryRadiance = 2, kQueryGather = 3, kQueryProbe = 4 };
+// its gather instance (points x samples) or its probe instance (probes x samples), or
+// rt_ambient_kernel (ambient.hip; points x samples).
+enum QueryKind {
+    kQueryClosest = 0,
+    kQueryAnyHit = 1,
+    kQueryRadiance = 2,
+    kQueryGather = 3,
+    kQueryProbe = 4,
+    kQueryAmbient = 5
+};
 
 // Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
 static const struct {
     uint32_t (*threads)(int mode, bool tris);
     hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-} kQueryKernels[5] = {{rt_query_threads, rt_query_occupancy},
+} kQueryKernels[6] = {{rt_query_threads, rt_query_occupancy},
                       {rt_occlusion_threads, rt_occlusion_occupancy},
                       {rt_radiance_threads, rt_radiance_occupancy},
                       {rt_radiance_threads, rt_gather_occupancy},
-                      {rt_radiance_threads, rt_probe_occupancy}};
+                      {rt_radiance_threads, rt_probe_occupancy},
+                      {rt_ambient_threads, rt_ambient_occupancy}};
 
 struct QueryLaunch {
     KernelArgs ka{};
@@ -2049,7 +2067,7 @@ static int query_buffers(rt_ctx* ctx, size_t n) {
     return RT_OK;
 }
 
-// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather, rt_probe_sh): the `count` records
+// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather, rt_probe_sh, rt_ambient): the `count` records
 // of `in_bytes` each at host pointer `in` go through the pinned and the device scratch in chunks of
 // "query_chunk"; run(device in, device out, n) answers a chunk, and `out_bytes` per record come
 // back to `out`. Both scratch buffers hold the inputs at their base and the results at capacity x
@@ -2642,6 +2660,73 @@ int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance, uint6
     return staged_query(ctx, points, sizeof(rt_gather_point), radiance, 16, count, true, segments,
                         [&](const void* d_pts, void* d_rad, uint64_t n) {
                             return run_gather(ctx, d_pts, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs);
+                        });
+}
+
+// ---- ambient queries (ambient.hip) ---------------------------------------------------------------
+//
+// Per point, the open count and the sum of the open directions among `samples` any-hit searches
+// through the gather's lobe (the contract in include/rt_abi.h), with the scene visibility and the
+// absence of side effects of rt_occluded. rt_ambient_kernel runs (point, stripe) items into the
+// gather's partials; rt_gather_resolve_kernel reduces each point's partials.
+
+// The most samples per point: `open` stays an exactly represented integer (2^24).
+constexpr uint32_t kMaxAmbientSamples = 1u << 24;
+
+// Answers `count` points at device pointer `points` into `out`, stream-ordered on the primary
+// stream, in launches of at most "gather_chunk" points.
+static int run_ambient(rt_ctx* ctx, const void* points, void* out, uint64_t count, uint32_t first_sample,
+                       uint32_t samples) {
+    if (count == 0) return RT_OK;
+    QueryLaunch q;
+    // the placement threshold of the other queries, on the walks the call runs at most
+    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
+    int rc = query_scene(ctx, walks, kQueryAmbient, q);
+    if (rc) return rc;
+    const uint32_t stripes = std::min<uint32_t>(samples, 64u);
+    const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
+    if ((rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u))) return rc;
+    for (uint64_t done = 0; done < count;) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
+        // the launch is sized by its items, (point, stripe) pairs: at most 2^20 x 64
+        const uint64_t items = (uint64_t)n * stripes;
+        const rtq::QuerySchedule s = rtq::query_schedule(items, q.waves_per_block, q.resident,
+                                                         rtq::kRadianceFirstChunkMax, rtq::kRadianceChunkMax);
+        RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+        hipError_t e = rt_launch_ambient(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s,
+                                         static_cast<const unsigned char*>(points) + done * sizeof(rt_ambient_point),
+                                         ctx->d_gather_partials, items, ctx->d_query_next, first_sample, samples,
+                                         stripes, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, "rt_ambient_kernel launch", e);
+        e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(out) + done * 16u, n, stripes,
+                                     ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, "rt_gather_resolve_kernel launch", e);
+        done += n;
+    }
+    return RT_OK;
+}
+
+int rt_ambient_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count, uint32_t first_sample,
+                      uint32_t samples) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_ambient_device: samples is 0");
+    if (samples > kMaxAmbientSamples) return fail(ctx, RT_E_INVALID, "rt_ambient_device: samples above 16777216");
+    if (count == 0) return RT_OK;
+    int rc = check_device_ptrs(ctx, "rt_ambient_device", {{points_device, "points", 16, false}, {out_device, "out", 16, false}});
+    if (rc || (rc = query_enter(ctx))) return rc;
+    return run_ambient(ctx, points_device, out_device, count, first_sample, samples);
+}
+
+int rt_ambient(rt_ctx* ctx, const rt_ambient_point* points, float* out, uint64_t count, uint32_t first_sample,
+               uint32_t samples) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_ambient: samples is 0");
+    if (samples > kMaxAmbientSamples) return fail(ctx, RT_E_INVALID, "rt_ambient: samples above 16777216");
+    if (count == 0) return RT_OK;
+    if (!points || !out) return fail(ctx, RT_E_INVALID, "rt_ambient: points or out is NULL");
+    return staged_query(ctx, points, sizeof(rt_ambient_point), out, 16, count, false, nullptr,
+                        [&](const void* d_pts, void* d_out, uint64_t n) {
+                            return run_ambient(ctx, d_pts, d_out, n, first_sample, samples);
                         });
 }
 

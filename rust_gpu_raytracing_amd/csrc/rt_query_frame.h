@@ -213,6 +213,19 @@ __device__ __forceinline__ uint32_t rank_among(uint64_t need) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
 }
 
+// ---- directions drawn on the device ------------------------------------------------------------
+
+// Step 2 of the gather contract (and of the ambient contract, which refers to it): the direction
+// of the sample with index u of a point with normal n, used as given. The gather instance of
+// rt_radiance_kernel and rt_ambient_kernel both call this, so both hold the same bits.
+__device__ __forceinline__ f3 gather_direction(f3 n, uint32_t stream, uint32_t u) {
+    uint32_t dseed = (stream * u * 326624u) ^ 0x9E3779B9u;
+    const float gx = normal01(dseed);
+    const float gy = normal01(dseed);
+    const float gz = normal01(dseed);
+    return normalize(n + mk(gx, gy, gz));
+}
+
 // ---- the traversal step --------------------------------------------------------------------------
 
 // Lane states. A lane owns one ray at a time.

@@ -522,6 +522,77 @@ class Renderer:
         cur.wait_stream(mine)
         return (out, int(segments.item())) if return_segments else out
 
+    # ------------------------------------------------------------------ ambient queries
+    def ambient(self, points, streams=None, t_max=np.inf, samples: int = 64, first_sample: int = 1,
+                device: bool = False):
+        """How open the hemisphere over each surface point is (rt_ambient): per point, ``open``, the
+        number of ``samples`` directions through the gather's lobe that nothing blocks before
+        ``t_max``, and ``bent``, the sum of those directions. Ambient occlusion is
+        ``open / samples``, the bent normal ``bent`` normalised. The directions are drawn on the
+        device and each is one any-hit search of ``occluded``; the sums are the contract's
+        stripe-and-tree reduction (include/rt_abi.h), bit-exact whatever the schedule. Only
+        geometry matters. Against the scene as it is now, without touching anything a render reads.
+
+        ``points``: an (n, 6) float32 array (position, normal; the normal is used as given), with
+        ``streams`` an (n,) uint32 array of RNG streams (default: 1 + the point's position in the
+        batch) and ``t_max`` a scalar or an (n,) array (+inf: sky visibility), or a
+        ``buffers.AMBIENT_POINT`` array. Returns ``(bent, open)``: (n, 3) and (n,) float32 arrays.
+        With ``device`` the records are uploaded and answered by rt_ambient_device -- stream-ordered
+        on the context's stream -- and CUDA tensors come back; a CUDA torch tensor of shape (n, 8)
+        float32 (rt_ambient_point records: the stream's bits in column 3, t_max in column 7)
+        always goes that way."""
+        if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+            if streams is not None:
+                raise ValueError("device points carry their stream in column 3 and t_max in column 7")
+            return self._ambient_device(points, first_sample, samples)
+        points = np.asarray(points)
+        if points.dtype == B.AMBIENT_POINT:
+            if streams is not None:
+                raise ValueError("AMBIENT_POINT records carry their own stream and t_max")
+        else:
+            r = np.ascontiguousarray(points, np.float32)
+            if r.ndim != 2 or r.shape[1] != 6:
+                raise ValueError("points must be (n, 6) float32 or an AMBIENT_POINT array")
+            points = np.zeros(r.shape[0], B.AMBIENT_POINT)
+            points["position"] = r[:, :3]
+            points["normal"] = r[:, 3:]
+            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
+            if s.shape != (r.shape[0],):
+                raise ValueError("streams must be an (n,) array")
+            points["stream"] = s
+            bound = np.asarray(t_max, np.float32)
+            if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != r.shape[0]):
+                raise ValueError("t_max must be a scalar or an (n,) array")
+            points["t_max"] = bound
+        points = np.ascontiguousarray(points.reshape(-1))
+        if device:
+            import torch
+
+            t = torch.from_numpy(points.view(np.float32).reshape(-1, 8).copy()).to(f"cuda:{self.device}")
+            return self._ambient_device(t, first_sample, samples)
+        out = np.zeros((points.shape[0], 4), np.float32)
+        self._call("rt_ambient", N.ptr(points), N.ptr(out), points.shape[0], int(first_sample), int(samples))
+        return out[:, :3].copy(), out[:, 3].copy()
+
+    def _ambient_device(self, points, first_sample, samples):
+        import torch
+
+        if not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
+            raise ValueError("device points must be a CUDA float32 tensor of shape (n, 8)")
+        if points.device.index != self.device:
+            raise ValueError("device points must live on the renderer's device")
+        points = points.contiguous()
+        out = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+        # the stream handshake of _trace_rays_device
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=points.device)
+        cur = torch.cuda.current_stream(points.device)
+        mine.wait_stream(cur)
+        self._call("rt_ambient_device", ctypes.c_void_p(points.data_ptr() if points.shape[0] else None),
+                   ctypes.c_void_p(out.data_ptr() if points.shape[0] else None), points.shape[0], int(first_sample),
+                   int(samples))
+        cur.wait_stream(mine)
+        return out[:, :3], out[:, 3]
+
     # ------------------------------------------------------------------ probe queries
     def probe_sh(self, positions, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,
                  samples: int = 256, return_segments: bool = False):

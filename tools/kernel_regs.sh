@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-kernel register use / spills / occupancy of pathtrace.hip (device-only compile, a few seconds).
-# usage: tools/kernel_regs.sh [query.hip | occlusion.hip | radiance.hip | denoise.hip | display.hip] [extra hipcc flags]
-# With a source name: every kernel of that file of csrc/ instead (rt_query_kernel / rt_occlusion_kernel /
+# usage: tools/kernel_regs.sh [query.hip | occlusion.hip | ambient.hip | radiance.hip | denoise.hip | display.hip] [extra hipcc flags]
+# With a source name: every kernel of that file of csrc/ instead (rt_query_kernel / rt_occlusion_kernel / rt_ambient_kernel /
 # rt_radiance_kernel instances as <mode, triangles, threads>, the latter also <..., kind>: 0 radiance,
 # 1 gather, 2 probe; display.hip:
 # rt_display_meter_kernel, rt_display_solve_kernel and rt_display_tone_kernel instances as <operator, encode>).

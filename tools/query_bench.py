@@ -1,7 +1,7 @@
 """Throughput of the ray-query kernel (rt_trace_rays_device) and its placement crossover.
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
-                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather] [--probe]
+                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather] [--probe] [--ambient]
                                    [--out profiles/query_bench.jsonl]
 
 Rays: the configuration's width x height camera rays (coherent: neighbouring rays are
@@ -54,6 +54,17 @@ folded streams) and traced by one rt_radiance_device call with samples = 1 and f
 both record orders. Each round checks that all trace equal segments and that steps 4 and 5 of the
 probe contract over the by-hand results (torch's f32 multiply and add, one operation each) equal
 the probe call bit for bit.
+--ambient: the ambient query (rt_ambient_device) against the two ways to get its answer without
+it, in one process per configuration of --ambient-configs (c2_rtiow and c3_chess), after a warm-up
+of each. --points points (here 65,536 by default) are taken from the first hits of
+the camera rays, streams 1..n, at --samples samples (here 256), all with the bound --t-max. Series:
+(a) rt_ambient_device; (b) rt_gather_device at bounces = 1 on the same points (the path tracer per
+sample); (c) rt_occluded_device fed the contract's n x samples records (o, dir, t_max), made once on
+the host (tools/gather_records.c) and already resident in device memory: the walk-only floor, which
+leaves out the transfer of 32 B per sample that a caller would pay. Each round checks that the
+open counts of (a) equal samples minus the sums of (c)'s bytes, and that the contract's tree over
+(c)'s terms equals (a) bit for bit. Device events on the context's stream; median, minimum and
+maximum over --rounds.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -520,6 +531,119 @@ def probe_bench(r, args, scene, bounces, dev, emit):
          zero_draws=zero_draws, build=r._lib.rt_build_hash().decode(), **row)
 
 
+def ambient_bench(r, args, scene, config, dev, emit):
+    """The --ambient series of one configuration (module docstring)."""
+    import statistics
+
+    import torch
+
+    n, samples, first = args.points, args.samples, 1
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+    P = ctypes.c_void_p
+
+    # the points: first hits of the camera rays, spread evenly over the image
+    q = camera_query_rays(scene)
+    q_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    hits_t = torch.empty((q.shape[0], 16), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    r._call("rt_trace_rays_device", P(q_t.data_ptr()), P(hits_t.data_ptr()), q.shape[0])
+    r.synchronize()
+    h = hits_t.cpu().numpy().view(B.HIT).reshape(-1)
+    hit = np.nonzero(h["kind"] != B.HIT_MISS)[0]
+    assert hit.shape[0] >= n, (hit.shape[0], n)
+    pick = hit[np.linspace(0, hit.shape[0] - 1, n).astype(np.int64)]
+    points = np.zeros(n, B.AMBIENT_POINT)
+    points["position"], points["normal"] = h["position"][pick], h["normal"][pick]
+    points["stream"] = 1 + np.arange(n, dtype=np.uint32)
+    points["t_max"] = args.t_max
+    del q_t, hits_t
+
+    # (c)'s records, point-major: a radiance record's pad is an occlusion record's t_max
+    helper = build_gather_records()
+    t0 = time.perf_counter()
+    records = np.zeros((n * samples, 8), np.float32)
+    helper.gather_records(points.ctypes.data, n, first, samples, 1, records.ctypes.data)
+    records[:, 7] = args.t_max
+    host_ms = (time.perf_counter() - t0) * 1e3
+    rec_t = torch.from_numpy(records).to(dev)
+    points_t = torch.from_numpy(points.view(np.float32).reshape(-1, 8)).to(dev)
+    out_t = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    gather_t = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    bytes_t = torch.empty((n * samples,), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+
+    def ambient():
+        r._call("rt_ambient_device", P(points_t.data_ptr()), P(out_t.data_ptr()), n, first, samples)
+
+    def gather():
+        r._call("rt_gather_device", P(points_t.data_ptr()), P(gather_t.data_ptr()), n, 1, first, samples, None)
+
+    def occluded():
+        r._call("rt_occluded_device", P(rec_t.data_ptr()), P(bytes_t.data_ptr()), n * samples)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record(stream)
+        fn()
+        t1.record(stream)
+        t1.synchronize()
+        return t0.elapsed_time(t1)
+
+    def same_as_occluded():  # steps 4 and 5 over (c)'s bytes: torch's f32 add is the IEEE one
+        r.synchronize()
+        v = (1 - bytes_t.view(n, samples)).to(torch.float32)
+        ok = bool(torch.equal(v.sum(dim=1, dtype=torch.float64).to(torch.float32), out_t[:, 3]))
+        p = torch.zeros((n, 64, 4), dtype=torch.float32, device=dev)
+        d = rec_t.view(n, samples, 8)[..., 4:7]
+        for k in range(0, samples, 64):
+            m = min(64, samples - k)
+            open_k = v[:, k:k + m, None]
+            terms = torch.cat([torch.where(open_k != 0, d[:, k:k + m], torch.zeros_like(d[:, k:k + m])), open_k], dim=2)
+            p[:, :m] = p[:, :m] + terms
+        off = 32
+        while off:
+            p[:, :off] = p[:, :off] + p[:, off:2 * off]
+            off //= 2
+        ok = ok and bool(torch.equal(p[:, 0].contiguous().view(torch.int32), out_t.view(torch.int32)))
+        torch.cuda.synchronize()
+        return ok
+
+    for fn in (ambient, gather, occluded):
+        fn()  # warm-up of every shape and placement
+    r.synchronize()
+    ms = {"ambient": [], "gather_b1": [], "occluded_resident": []}
+    same = []
+    for _ in range(args.rounds):
+        out_t.zero_()
+        bytes_t.zero_()
+        torch.cuda.synchronize()
+        ms["ambient"].append(timed(ambient))
+        ms["gather_b1"].append(timed(gather))
+        ms["occluded_resident"].append(timed(occluded))
+        same.append(same_as_occluded())
+        assert same[-1], "the tree over rt_occluded's bytes differs from rt_ambient"
+    med = statistics.median
+    row = {k + "_ms": round(med(v), 3) for k, v in ms.items()}
+    row.update({k + "_ms_min": round(min(v), 3) for k, v in ms.items()})
+    row.update({k + "_ms_max": round(max(v), 3) for k, v in ms.items()})
+    emit(kind="ambient", config=config, points=n, samples=samples, t_max=args.t_max, rounds=args.rounds,
+         searches=n * samples, open_fraction=round(float(out_t[:, 3].sum(dtype=torch.float64).item()) / (n * samples), 4),
+         bit_identical_to_occluded=all(same),
+         ambient_over_gather=round(med(ms["ambient"]) / med(ms["gather_b1"]), 4),
+         ambient_over_occluded=round(med(ms["ambient"]) / med(ms["occluded_resident"]), 4),
+         ambient_msearch_s=round(n * samples / med(ms["ambient"]) / 1e3, 1),
+         records_host_ms=round(host_ms, 1), records_mb=round(records.nbytes / 2 ** 20, 1),
+         build=r._lib.rt_build_hash().decode(), **row)
+
+
+def lines_out(args, lines):
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            for rec in lines:
+                f.write(json.dumps(rec) + "\n")
+
+
 def main():
     import torch
 
@@ -534,8 +658,14 @@ def main():
     ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
     ap.add_argument("--gather", action="store_true", help="the gather query against the same paths done by hand")
     ap.add_argument("--probe", action="store_true", help="the probe query against the same paths done by hand")
-    ap.add_argument("--points", type=int, default=4096, help="--gather: surface points; --probe: probes")
-    ap.add_argument("--samples", type=int, default=1024, help="--gather, --probe: samples per point")
+    ap.add_argument("--ambient", action="store_true",
+                    help="the ambient query against the gather at one bounce and the resident occlusion records")
+    ap.add_argument("--ambient-configs", default="c2_rtiow,c3_chess", help="--ambient: the configurations, in one process")
+    ap.add_argument("--t-max", type=float, default=1.0, help="--ambient: the bound of every point, in world units")
+    ap.add_argument("--points", type=int, default=None,
+                    help="--gather: surface points; --probe: probes (4096); --ambient: surface points (65536)")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="--gather, --probe: samples per point (1024); --ambient: samples per point (256)")
     ap.add_argument("--bounces", type=int, default=None,
                     help="--radiance, --gather, --probe: bounce limit (default: the configuration's)")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="--radiance: untimed work before the rounds")
@@ -546,6 +676,10 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "query_bench needs a HIP device"
     dev = torch.device("cuda:0")
+    if args.points is None:
+        args.points = 65536 if args.ambient else 4096
+    if args.samples is None:
+        args.samples = 256 if args.ambient else 1024
     scene, bounces = build_config(args.config, width=args.width, height=args.height)
     q = camera_query_rays(scene)
     n = q.shape[0]
@@ -559,7 +693,8 @@ def main():
     lines = []
 
     def emit(**kw):
-        rec = dict(config=args.config, width=args.width, height=args.height, **kw)
+        rec = dict(config=args.config, width=args.width, height=args.height)
+        rec.update(kw)
         if tuning:
             rec["tuning"] = tuning
         lines.append(rec)
@@ -567,6 +702,13 @@ def main():
 
     call = "rt_occluded_device" if args.occluded else "rt_trace_rays_device"
     tuning = {k: int(v) for k, v in (kv.split("=", 1) for kv in args.tune)}
+    if args.ambient:
+        for config in args.ambient_configs.split(","):
+            scene, _ = build_config(config, width=args.width, height=args.height)
+            with Renderer(scene, tuning=tuning) as r:
+                ambient_bench(r, args, scene, config, dev, emit)
+        lines_out(args, lines)
+        return
     with Renderer(scene, tuning=tuning) as r:
         if args.probe:
             probe_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
@@ -607,11 +749,7 @@ def main():
             s = time.perf_counter() - t0
             emit(kind="render", frames=args.frames, bounces=bounces, ms_per_frame=round(s * 1e3 / args.frames, 4),
                  mray_s=round(r.ray_count() / s / 1e6, 1))
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        with open(args.out, "a") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
+    lines_out(args, lines)
 
 
 if __name__ == "__main__":
