@@ -25,7 +25,7 @@ SOURCES = [CSRC / "pathtrace.hip", CSRC / "query.hip", CSRC / "occlusion.hip", C
 HEADERS = [CSRC / "rt_bvh_slab.h", CSRC / "rt_device_math.h", CSRC / "rt_kernel_args.h", CSRC / "sphere_bvh.h",
            CSRC / "rt_scene_math.h", CSRC / "tri_qnode.h", CSRC / "tri_cone.h", CSRC / "rt_path_common.h",
            CSRC / "rt_walk.h", CSRC / "rt_sphere_roots.h", CSRC / "rt_sphere_walk.h", CSRC / "rt_query_frame.h", CSRC / "rt_occlusion_walk.h",
-           CSRC / "rt_query_schedule.h", INCLUDE / "rt_abi.h"]
+           CSRC / "rt_query_schedule.h", CSRC / "rt_launch.h", INCLUDE / "rt_abi.h"]
 
 ARCH = os.environ.get("RT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -75,6 +75,7 @@ def hipcc_command(out: Path = OUT, extra: list[str] | None = None, build_hash: s
         *map(str, SOURCES),
         "-ldl",  # rt_multi.cpp opens librccl at run time (dlopen), only for rt_create_multi
         "-pthread",  # rt_multi.cpp: one host thread per device of a group
+        "-Wl,--no-undefined",  # a launcher of rt_launch.h that nothing defines fails here, not at its first call
         "-o",
         str(out),
     ]

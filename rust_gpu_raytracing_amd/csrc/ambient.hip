@@ -46,6 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_occlusion_walk.h"
 #include "rt_path_common.h"
 #include "rt_query_frame.h"

@@ -152,6 +152,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_launch.h"
 #include "rt_path_common.h"
 
 #pragma clang fp contract(off)

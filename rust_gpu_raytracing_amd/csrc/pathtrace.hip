@@ -25,6 +25,7 @@
 
 #include <algorithm>
 
+#include "rt_launch.h"
 #include "rt_path_common.h"
 #include "rt_sphere_walk.h"
 #include "rt_walk.h"

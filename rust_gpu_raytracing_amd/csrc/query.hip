@@ -20,6 +20,7 @@
 
 #include <algorithm>
 
+#include "rt_launch.h"
 #include "rt_path_common.h"
 #include "rt_query_frame.h"
 #include "rt_walk.h"

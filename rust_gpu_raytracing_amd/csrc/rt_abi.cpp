@@ -22,103 +22,12 @@
 
 #include "rt_abi.h"
 #include "rt_kernel_args.h"
+#include "rt_launch.h"
 #include "rt_query_schedule.h"
 #include "rt_scene_math.h"
 #include "sphere_bvh.h"
 #include "tri_cone.h"
 #include "tri_qnode.h"
-
-hipError_t rt_launch_math_selftest(uint32_t which, unsigned long long* mismatches, uint32_t* first_bad,
-                                   hipStream_t stream);
-hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
-                               size_t lds_bytes, uint32_t blocks, hipStream_t stream);
-hipError_t rt_pathtrace_pick_config(int mode, bool tris, bool frame_par, size_t lds_bytes,
-                                    size_t lds_bytes_per_thread, uint32_t force_threads, uint32_t waves_cap,
-                                    uint32_t* threads, int* blocks_per_cu);
-hipError_t rt_launch_edit(const float* model, const uint32_t* tri_object, const uint32_t* sub_object,
-                          const uint2* object_tris, const rt_scene::Placement* place, uint32_t object_count,
-                          uint32_t n_tri, uint32_t n_sub, RtTriangleHot* tris, float4* bounds, RtSubObject* subs,
-                          RtObject* objects, hipStream_t stream);
-hipError_t rt_launch_quantize_tri_nodes(const SphereBvhNode* nodes, uint32_t n, const uint32_t* src,
-                                        const uint32_t* skip, uint32_t n_out, SphereBvhNode* out32, uint4* q,
-                                        float4* grid, hipStream_t stream);
-hipError_t rt_launch_refit(SphereBvhNode* nodes, const SubObjectPrim* prims, const RtSubObject* subs,
-                           const uint32_t* order, const uint32_t* level_offsets, uint32_t n_levels, float* extent_out,
-                           hipStream_t stream);
-hipError_t rt_launch_tri_leafcert(const SubObjectPrim* prims, uint32_t n_prims, const RtSubObject* subs,
-                                  const RtTriangleHot* tris, uint32_t n_tri, TriLeafCert* out, hipStream_t stream);
-hipError_t rt_launch_tri_leaftris(const SubObjectPrim* prims, uint32_t n_prims, const RtTriangleHot* tris,
-                                  uint32_t n_tri, uint4* out, hipStream_t stream);
-hipError_t rt_launch_primary(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t threads,
-                             uint32_t min_waves, hipStream_t stream);
-hipError_t rt_launch_brute_wf(const KernelArgs& ka, bool tris, bool scalar_stream, size_t lds_bytes, uint32_t blocks,
-                              hipStream_t stream);
-size_t rt_brute_wf_tile_bytes(bool scalar_stream);
-uint32_t rt_brute_wf_chunk();
-// the query kernels (query.hip, occlusion.hip, radiance.hip, ambient.hip): per kernel the workgroup size of a
-// placement, the resident workgroups per CU, and the launch on a schedule of rt_query_schedule.h
-uint32_t rt_query_threads(int mode, bool tris);
-hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
-                           const void* rays, void* hits, uint64_t count, unsigned long long* counter,
-                           hipStream_t stream);
-uint32_t rt_occlusion_threads(int mode, bool tris);
-hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
-                               const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
-                               hipStream_t stream);
-uint32_t rt_radiance_threads(int mode, bool tris);
-hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
-                              const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
-                              unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
-                              hipStream_t stream);
-hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
-                                    hipStream_t stream);
-uint32_t rt_ambient_threads(int mode, bool tris);
-hipError_t rt_ambient_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
-                             const void* points, void* partials, uint64_t count, unsigned long long* counter,
-                             uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
-hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
-                                 const void* probes, void* lights, uint64_t count, unsigned long long* counter,
-                                 unsigned long long* segments, uint32_t first_sample, uint32_t samples,
-                                 hipStream_t stream);
-hipError_t rt_launch_probe_resolve(const void* lights, const void* probes, void* sh, uint32_t count, uint32_t first_sample,
-                                   uint32_t samples, hipStream_t stream);
-hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
-hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
-hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
-                                     const void* hits, float4* plane_a, float4* plane_b, hipStream_t stream);
-hipError_t rt_launch_denoise_init(const float4* accum, float4* dst, uint32_t* packed, uint64_t n, float div,
-                                  hipStream_t stream);
-hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
-                                  uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
-                                  float sigma_depth, bool lds, hipStream_t stream, const float4* nn = nullptr);
-hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
-                              float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
-                              uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
-                              hipStream_t stream);
-hipError_t rt_launch_display_meter(const float4* src, uint64_t n, float div, uint32_t* bins, hipStream_t stream);
-hipError_t rt_launch_display_solve(uint32_t* bins, uint32_t* kept, uint32_t* state, uint32_t low_permille,
-                                   uint32_t high_permille, float key, float min_exposure, float max_exposure,
-                                   float adaptation, bool has_state, hipStream_t stream);
-hipError_t rt_launch_display_tone(const float4* src, uint32_t* dst, uint64_t n, float div, const uint32_t* state,
-                                  float exposure, float iw2, const float* srgb, uint32_t op, uint32_t encode,
-                                  hipStream_t stream);
-hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
-                             uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
-                             uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
-hipError_t rt_launch_pack_output(uint32_t* output, uint32_t* packed, uint32_t width, uint32_t height, uint32_t tiles_x,
-                                 uint32_t n_tiles, uint32_t first_rank, uint32_t ranks, uint32_t world,
-                                 uint64_t stride_px, uint32_t skip_rank, bool unpack, hipStream_t stream);
-hipError_t rt_launch_pack(const float4* accum, float4* dst, uint32_t width, uint32_t height, uint32_t tiles_x,
-                          uint32_t owned_tiles, uint32_t rank, uint32_t world, hipStream_t stream);
-hipError_t rt_launch_unpack(const float4* src, float4* accum, uint32_t* output, uint32_t width, uint32_t height,
-                            uint32_t tiles_x, uint32_t n_tiles, uint32_t first_rank, uint32_t ranks, uint32_t world,
-                            uint64_t stride_px, uint32_t skip_rank, float divisor, hipStream_t stream);
 
 static_assert(sizeof(rt_params) == 48, "Params is 48 bytes (src/buffers.rs:9-22)");
 static_assert(sizeof(rt_ray_camera) == 16, "RayCamera is 16 bytes");
@@ -2067,20 +1976,67 @@ static int query_buffers(rt_ctx* ctx, size_t n) {
     return RT_OK;
 }
 
-// One staged query call (rt_trace_rays, rt_occluded, rt_radiance, rt_gather, rt_probe_sh, rt_ambient): the `count` records
-// of `in_bytes` each at host pointer `in` go through the pinned and the device scratch in chunks of
-// "query_chunk"; run(device in, device out, n) answers a chunk, and `out_bytes` per record come
-// back to `out`. Both scratch buffers hold the inputs at their base and the results at capacity x
-// 32 bytes (where the records of a closest-hit chunk go); a call whose results exceed 32 bytes per
-// record (rt_probe_sh: 144) sizes both by that many records more. With `count_segments` the context's
-// segment counter is zeroed first and read back after the last chunk, into the pinned bytes after
-// a chunk's results, for `segments` (which may be null).
+// What the two entry points of a query family differ in from those of the other families; the rest
+// of an entry point is staged_query (the host form) or device_query (the device form) around the
+// family's run(device in, device out, n, device segment counter or null).
+struct QueryFamily {
+    const char* host;      // the entry points, as the messages name them
+    const char* device;
+    const char* in;        // the record arguments, as the messages name them
+    const char* out;
+    size_t in_bytes;       // per record
+    size_t out_bytes;
+    uintptr_t out_align;   // of the device form's `out` (its `in` is 16-byte aligned, `segments` 8)
+    uint32_t max_samples;  // 0: the family takes no `samples`
+    bool segments;         // the family counts ray segments
+};
+constexpr uint32_t kAnySamples = UINT32_MAX;
+
+// The checks on `samples`, which come first: an entry point refuses them whatever `count` is.
+static int check_samples(rt_ctx* ctx, const QueryFamily& f, const char* entry, uint32_t samples) {
+    if (f.max_samples == 0) return RT_OK;
+    if (samples == 0) return fail(ctx, RT_E_INVALID, std::string(entry) + ": samples is 0");
+    if (samples > f.max_samples)
+        return fail(ctx, RT_E_INVALID, std::string(entry) + ": samples above " + std::to_string(f.max_samples));
+    return RT_OK;
+}
+
+// The device form of a family's entry point: `count` records at device pointer `in` answered into
+// `out`, stream-ordered on the primary stream; `segments` (device memory too) may be null.
 extern "C++" template <class Run>  // (a template inside the extern "C" block of the entry points)
-static int staged_query(rt_ctx* ctx, const void* in, size_t in_bytes, void* out, size_t out_bytes, uint64_t count,
-                        bool count_segments, uint64_t* segments, Run run) {
-    int rc = query_enter(ctx);
+static int device_query(rt_ctx* ctx, const QueryFamily& f, const void* in, void* out, uint64_t count, uint32_t samples,
+                        void* segments, Run run) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_samples(ctx, f, f.device, samples);
+    if (rc || count == 0) return rc;
+    rc = check_device_ptrs(ctx, f.device,
+                           {{in, f.in, 16, false}, {out, f.out, f.out_align, false}, {segments, "segments", 8, true}});
+    if (rc || (rc = query_enter(ctx))) return rc;
+    return run(in, out, count, static_cast<unsigned long long*>(segments));
+}
+
+// The host form of a family's entry point: the `count` records of `in_bytes` each at host pointer
+// `in` go through the pinned and the device scratch in chunks of "query_chunk"; run answers a
+// chunk, and `out_bytes` per record come back to `out`. Both scratch buffers hold the inputs at
+// their base and the results at capacity x 32 bytes (where the records of a closest-hit chunk go);
+// a call whose results exceed 32 bytes per record (rt_probe_sh: 144) sizes both by that many
+// records more. In a family that counts segments the context's segment counter is zeroed first and
+// read back after the last chunk, into the pinned bytes after a chunk's results, for `segments`
+// (which may be null).
+extern "C++" template <class Run>
+static int staged_query(rt_ctx* ctx, const QueryFamily& f, const void* in, void* out, uint64_t count, uint32_t samples,
+                        uint64_t* segments, Run run) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_samples(ctx, f, f.host, samples);
     if (rc) return rc;
-    if (count_segments && !ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    if (count == 0) {
+        if (segments) *segments = 0;
+        return RT_OK;
+    }
+    if (!in || !out) return fail(ctx, RT_E_INVALID, std::string(f.host) + ": " + f.in + " or " + f.out + " is NULL");
+    if ((rc = query_enter(ctx))) return rc;
+    if (f.segments && !ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    const size_t in_bytes = f.in_bytes, out_bytes = f.out_bytes;
     const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
     if ((rc = query_buffers(ctx, chunk * ((out_bytes + 31u) / 32u)))) return rc;
     unsigned char* d_in = static_cast<unsigned char*>(ctx->d_query_buf);
@@ -2088,39 +2044,43 @@ static int staged_query(rt_ctx* ctx, const void* in, size_t in_bytes, void* out,
     unsigned char* h_in = static_cast<unsigned char*>(ctx->query_pinned);
     unsigned char* h_out = h_in + ctx->query_pinned_rays * sizeof(rt_query_ray);
     unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_out + chunk * out_bytes);
-    if (count_segments)
-        RT_HIP(ctx, hipMemsetAsync(ctx->d_radiance_segs, 0, sizeof(unsigned long long), ctx->stream));
+    unsigned long long* d_segs = f.segments ? ctx->d_radiance_segs : nullptr;
+    if (d_segs) RT_HIP(ctx, hipMemsetAsync(d_segs, 0, sizeof(unsigned long long), ctx->stream));
     for (uint64_t done = 0; done < count;) {
         const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
         std::memcpy(h_in, static_cast<const unsigned char*>(in) + done * in_bytes, n * in_bytes);
         RT_HIP(ctx, hipMemcpyAsync(d_in, h_in, n * in_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run(d_in, d_out, n))) return rc;
+        if ((rc = run(d_in, d_out, n, d_segs))) return rc;
         RT_HIP(ctx, hipMemcpyAsync(h_out, d_out, n * out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        if (count_segments && done + n == count)
-            RT_HIP(ctx, hipMemcpyAsync(h_segs, ctx->d_radiance_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                       ctx->stream));
+        if (d_segs && done + n == count)
+            RT_HIP(ctx, hipMemcpyAsync(h_segs, d_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         std::memcpy(static_cast<unsigned char*>(out) + done * out_bytes, h_out, n * out_bytes);
         done += n;
     }
-    if (count_segments && segments) *segments = *h_segs;
+    if (d_segs && segments) *segments = *h_segs;
     return RT_OK;
 }
 
+// The run of a path family (run_radiance, run_gather, run_probe_sh) with a call's scalars bound.
+extern "C++" template <class PathRun>
+static auto bind_path_run(PathRun run, rt_ctx* ctx, uint32_t bounces, uint32_t first_sample, uint32_t samples) {
+    return [=](const void* in, void* out, uint64_t n, unsigned long long* segs) {
+        return run(ctx, in, out, n, bounces, first_sample, samples, segs);
+    };
+}
+
+constexpr QueryFamily kTraceRays = {"rt_trace_rays", "rt_trace_rays_device", "rays", "hits", sizeof(rt_query_ray),
+                                    sizeof(rt_hit), 16, 0, false};
+
 int rt_trace_rays_device(rt_ctx* ctx, const void* rays_device, void* hits_device, uint64_t count) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_trace_rays_device", {{rays_device, "rays", 16, false}, {hits_device, "hits", 16, false}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_query(ctx, rays_device, hits_device, count);
+    return device_query(ctx, kTraceRays, rays_device, hits_device, count, 0, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_query(ctx, in, out, n); });
 }
 
 int rt_trace_rays(rt_ctx* ctx, const rt_query_ray* rays, rt_hit* hits, uint64_t count) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (count == 0) return RT_OK;
-    if (!rays || !hits) return fail(ctx, RT_E_INVALID, "rt_trace_rays: rays or hits is NULL");
-    return staged_query(ctx, rays, sizeof(rt_query_ray), hits, sizeof(rt_hit), count, false, nullptr,
-                        [&](const void* d_rays, void* d_hits, uint64_t n) { return run_query(ctx, d_rays, d_hits, n); });
+    return staged_query(ctx, kTraceRays, rays, hits, count, 0, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_query(ctx, in, out, n); });
 }
 
 int rt_pick(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hit) {
@@ -2507,21 +2467,17 @@ int rt_display_reset(rt_ctx* ctx) {
 // The any-hit counterpart of the calls above, with the same scene visibility and the same absence
 // of side effects; rt_occluded stages through the same buffers (32 B in, 1 B out per ray: the
 // bytes go where the records of a closest-hit chunk would).
+constexpr QueryFamily kOccluded = {"rt_occluded", "rt_occluded_device", "rays", "occluded", sizeof(rt_occlusion_ray),
+                                   1, 1, 0, false};
+
 int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_occluded_device",
-                               {{rays_device, "rays", 16, false}, {occluded_device, "occluded", 1, false}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_query(ctx, rays_device, occluded_device, count, true);
+    return device_query(ctx, kOccluded, rays_device, occluded_device, count, 0, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_query(ctx, in, out, n, true); });
 }
 
 int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (count == 0) return RT_OK;
-    if (!rays || !occluded) return fail(ctx, RT_E_INVALID, "rt_occluded: rays or occluded is NULL");
-    return staged_query(ctx, rays, sizeof(rt_occlusion_ray), occluded, 1, count, false, nullptr,
-                        [&](const void* d_rays, void* d_occ, uint64_t n) { return run_query(ctx, d_rays, d_occ, n, true); });
+    return staged_query(ctx, kOccluded, rays, occluded, count, 0, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_query(ctx, in, out, n, true); });
 }
 
 // ---- radiance queries (radiance.hip) -----------------------------------------------------------
@@ -2530,18 +2486,22 @@ int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, ui
 // calls above. rt_radiance stages through the same buffers (32 B in, 16 B out per ray: the sums go
 // where the records of a closest-hit chunk would).
 
-// The head of a radiance or gather launch (`kind`) of `count` records into `radiance`: zero bounces
-// are answered here (*answered), else `q` receives the scene view and the shading arguments.
-static int path_query_scene(rt_ctx* ctx, void* radiance, uint64_t count, uint32_t bounces, uint32_t samples, int kind,
-                            QueryLaunch& q, bool* answered) {
-    *answered = bounces == 0;
-    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
-        RT_HIP(ctx, hipMemsetAsync(radiance, 0, (size_t)count * 16u, ctx->stream));
-        return RT_OK;
-    }
-    // the placement threshold of the other queries, on the walks the call runs at least
-    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
-    const int rc = query_scene(ctx, walks, kind, q);
+// The answer of a path query of zero bounces, `out_bytes` per record: the bounce loop does not run
+// (:226), so there is no light and there are no segments.
+static int answer_zero_bounces(rt_ctx* ctx, void* out, uint64_t count, size_t out_bytes) {
+    RT_HIP(ctx, hipMemsetAsync(out, 0, (size_t)count * out_bytes, ctx->stream));
+    return RT_OK;
+}
+
+// The walks of `count` records of `samples` each, for the placement threshold of the other queries.
+static uint64_t query_walks(uint64_t count, uint32_t samples) {
+    return count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
+}
+
+// The head of a radiance, gather or probe launch (`kind`) of `count` records, `bounces` > 0: `q`
+// receives the scene view, placed by the walks the call runs at least, and the shading arguments.
+static int path_query_scene(rt_ctx* ctx, uint64_t count, uint32_t bounces, uint32_t samples, int kind, QueryLaunch& q) {
+    const int rc = query_scene(ctx, query_walks(count, samples), kind, q);
     if (rc) return rc;
     q.ka.bounces = bounces;
     q.ka.drain_threshold = ctx->drain_threshold;
@@ -2555,10 +2515,10 @@ static int path_query_scene(rt_ctx* ctx, void* radiance, uint64_t count, uint32_
 static int run_radiance(rt_ctx* ctx, const void* rays, void* radiance, uint64_t count, uint32_t bounces,
                         uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
     if (count == 0) return RT_OK;
+    if (bounces == 0) return answer_zero_bounces(ctx, radiance, count, 16u);
     QueryLaunch q;
-    bool answered;
-    const int rc = path_query_scene(ctx, radiance, count, bounces, samples, kQueryRadiance, q, &answered);
-    if (rc || answered) return rc;
+    const int rc = path_query_scene(ctx, count, bounces, samples, kQueryRadiance, q);
+    if (rc) return rc;
     const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident, rtq::kRadianceFirstChunkMax,
                                                      rtq::kRadianceChunkMax);
     RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
@@ -2568,32 +2528,19 @@ static int run_radiance(rt_ctx* ctx, const void* rays, void* radiance, uint64_t 
     return RT_OK;
 }
 
+constexpr QueryFamily kRadiance = {"rt_radiance", "rt_radiance_device", "rays", "radiance", sizeof(rt_radiance_ray),
+                                   16, 16, kAnySamples, true};
+
 int rt_radiance_device(rt_ctx* ctx, const void* rays_device, void* radiance_device, uint64_t count, uint32_t bounces,
                        uint32_t first_sample, uint32_t samples, void* segments_device) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_radiance_device: samples is 0");
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_radiance_device", {{rays_device, "rays", 16, false},
-                                                           {radiance_device, "radiance", 16, false},
-                                                           {segments_device, "segments", 8, true}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_radiance(ctx, rays_device, radiance_device, count, bounces, first_sample, samples,
-                        static_cast<unsigned long long*>(segments_device));
+    return device_query(ctx, kRadiance, rays_device, radiance_device, count, samples, segments_device,
+                        bind_path_run(run_radiance, ctx, bounces, first_sample, samples));
 }
 
 int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint64_t count, uint32_t bounces,
                 uint32_t first_sample, uint32_t samples, uint64_t* segments) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_radiance: samples is 0");
-    if (count == 0) {
-        if (segments) *segments = 0;
-        return RT_OK;
-    }
-    if (!rays || !radiance) return fail(ctx, RT_E_INVALID, "rt_radiance: rays or radiance is NULL");
-    return staged_query(ctx, rays, sizeof(rt_radiance_ray), radiance, 16, count, true, segments,
-                        [&](const void* d_rays, void* d_rad, uint64_t n) {
-                            return run_radiance(ctx, d_rays, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs);
-                        });
+    return staged_query(ctx, kRadiance, rays, radiance, count, samples, segments,
+                        bind_path_run(run_radiance, ctx, bounces, first_sample, samples));
 }
 
 // ---- gather queries (radiance.hip, kGather) -----------------------------------------------------
@@ -2602,19 +2549,17 @@ int rt_radiance(rt_ctx* ctx, const rt_radiance_ray* rays, float* radiance, uint6
 // include/rt_abi.h). The path kernel is the radiance kernel's gather instance over (point, stripe)
 // items; rt_gather_resolve_kernel reduces each point's partials.
 
-// Gathers at `count` points at device pointer `points` into `radiance`, stream-ordered on the
-// primary stream, in launches of at most "gather_chunk" points; the counted segments are added to
-// the device counter `segments` (null: not counted).
-static int run_gather(rt_ctx* ctx, const void* points, void* radiance, uint64_t count, uint32_t bounces,
-                      uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
-    if (count == 0) return RT_OK;
-    QueryLaunch q;
-    bool answered;
-    int rc = path_query_scene(ctx, radiance, count, bounces, samples, kQueryGather, q, &answered);
-    if (rc || answered) return rc;
+// The launches of a gather or an ambient call, which differ in their kernel: `count` points (32-byte
+// records) at device pointer `points` in launches of at most "gather_chunk" points, each
+// launch(schedule, its points, items, stripes) over (point, stripe) items into the context's
+// partials, which rt_gather_resolve_kernel reduces into `out`. `what` names the launch in an error.
+extern "C++" template <class Launch>
+static int run_striped(rt_ctx* ctx, const QueryLaunch& q, const void* points, void* out, uint64_t count,
+                       uint32_t samples, const char* what, Launch launch) {
     const uint32_t stripes = std::min<uint32_t>(samples, 64u);
     const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
-    if ((rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u))) return rc;
+    const int rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u);
+    if (rc) return rc;
     for (uint64_t done = 0; done < count;) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
         // the launch is sized by its items, (point, stripe) pairs: at most 2^20 x 64
@@ -2622,45 +2567,47 @@ static int run_gather(rt_ctx* ctx, const void* points, void* radiance, uint64_t 
         const rtq::QuerySchedule s = rtq::query_schedule(items, q.waves_per_block, q.resident,
                                                          rtq::kRadianceFirstChunkMax, rtq::kRadianceChunkMax);
         RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
-        hipError_t e = rt_launch_radiance(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s,
-                                          static_cast<const unsigned char*>(points) + done * sizeof(rt_gather_point),
-                                          ctx->d_gather_partials, items, ctx->d_query_next, segments, first_sample,
-                                          samples, stripes, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel (gather) launch", e);
-        e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(radiance) + done * 16u, n,
-                                     stripes, ctx->stream);
+        hipError_t e = launch(s, static_cast<const unsigned char*>(points) + done * sizeof(rt_gather_point), items, stripes);
+        if (e != hipSuccess) return hip_fail(ctx, what, e);
+        e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(out) + done * 16u, n, stripes,
+                                     ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, "rt_gather_resolve_kernel launch", e);
         done += n;
     }
     return RT_OK;
 }
 
+// Gathers at `count` points at device pointer `points` into `radiance`, stream-ordered on the
+// primary stream, in launches of at most "gather_chunk" points; the counted segments are added to
+// the device counter `segments` (null: not counted).
+static int run_gather(rt_ctx* ctx, const void* points, void* radiance, uint64_t count, uint32_t bounces,
+                      uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
+    if (count == 0) return RT_OK;
+    if (bounces == 0) return answer_zero_bounces(ctx, radiance, count, 16u);
+    QueryLaunch q;
+    const int rc = path_query_scene(ctx, count, bounces, samples, kQueryGather, q);
+    if (rc) return rc;
+    return run_striped(ctx, q, points, radiance, count, samples, "rt_radiance_kernel (gather) launch",
+                       [&](const rtq::QuerySchedule& s, const void* records, uint64_t items, uint32_t stripes) {
+                           return rt_launch_radiance(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, records,
+                                                     ctx->d_gather_partials, items, ctx->d_query_next, segments,
+                                                     first_sample, samples, stripes, ctx->stream);
+                       });
+}
+
+constexpr QueryFamily kGather = {"rt_gather", "rt_gather_device", "points", "radiance", sizeof(rt_gather_point),
+                                 16, 16, kAnySamples, true};
+
 int rt_gather_device(rt_ctx* ctx, const void* points_device, void* radiance_device, uint64_t count, uint32_t bounces,
                      uint32_t first_sample, uint32_t samples, void* segments_device) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_gather_device: samples is 0");
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_gather_device", {{points_device, "points", 16, false},
-                                                         {radiance_device, "radiance", 16, false},
-                                                         {segments_device, "segments", 8, true}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_gather(ctx, points_device, radiance_device, count, bounces, first_sample, samples,
-                      static_cast<unsigned long long*>(segments_device));
+    return device_query(ctx, kGather, points_device, radiance_device, count, samples, segments_device,
+                        bind_path_run(run_gather, ctx, bounces, first_sample, samples));
 }
 
 int rt_gather(rt_ctx* ctx, const rt_gather_point* points, float* radiance, uint64_t count, uint32_t bounces,
               uint32_t first_sample, uint32_t samples, uint64_t* segments) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_gather: samples is 0");
-    if (count == 0) {
-        if (segments) *segments = 0;
-        return RT_OK;
-    }
-    if (!points || !radiance) return fail(ctx, RT_E_INVALID, "rt_gather: points or radiance is NULL");
-    return staged_query(ctx, points, sizeof(rt_gather_point), radiance, 16, count, true, segments,
-                        [&](const void* d_pts, void* d_rad, uint64_t n) {
-                            return run_gather(ctx, d_pts, d_rad, n, bounces, first_sample, samples, ctx->d_radiance_segs);
-                        });
+    return staged_query(ctx, kGather, points, radiance, count, samples, segments,
+                        bind_path_run(run_gather, ctx, bounces, first_sample, samples));
 }
 
 // ---- ambient queries (ambient.hip) ---------------------------------------------------------------
@@ -2680,53 +2627,32 @@ static int run_ambient(rt_ctx* ctx, const void* points, void* out, uint64_t coun
     if (count == 0) return RT_OK;
     QueryLaunch q;
     // the placement threshold of the other queries, on the walks the call runs at most
-    const uint64_t walks = count > UINT64_MAX / samples ? UINT64_MAX : count * samples;
-    int rc = query_scene(ctx, walks, kQueryAmbient, q);
+    const int rc = query_scene(ctx, query_walks(count, samples), kQueryAmbient, q);
     if (rc) return rc;
-    const uint32_t stripes = std::min<uint32_t>(samples, 64u);
-    const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
-    if ((rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u))) return rc;
-    for (uint64_t done = 0; done < count;) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
-        // the launch is sized by its items, (point, stripe) pairs: at most 2^20 x 64
-        const uint64_t items = (uint64_t)n * stripes;
-        const rtq::QuerySchedule s = rtq::query_schedule(items, q.waves_per_block, q.resident,
-                                                         rtq::kRadianceFirstChunkMax, rtq::kRadianceChunkMax);
-        RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
-        hipError_t e = rt_launch_ambient(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s,
-                                         static_cast<const unsigned char*>(points) + done * sizeof(rt_ambient_point),
-                                         ctx->d_gather_partials, items, ctx->d_query_next, first_sample, samples,
-                                         stripes, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, "rt_ambient_kernel launch", e);
-        e = rt_launch_gather_resolve(ctx->d_gather_partials, static_cast<unsigned char*>(out) + done * 16u, n, stripes,
-                                     ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, "rt_gather_resolve_kernel launch", e);
-        done += n;
-    }
-    return RT_OK;
+    return run_striped(ctx, q, points, out, count, samples, "rt_ambient_kernel launch",
+                       [&](const rtq::QuerySchedule& s, const void* records, uint64_t items, uint32_t stripes) {
+                           return rt_launch_ambient(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, records,
+                                                    ctx->d_gather_partials, items, ctx->d_query_next, first_sample,
+                                                    samples, stripes, ctx->stream);
+                       });
 }
+
+constexpr QueryFamily kAmbient = {"rt_ambient", "rt_ambient_device", "points", "out", sizeof(rt_ambient_point),
+                                  16, 16, kMaxAmbientSamples, false};
 
 int rt_ambient_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count, uint32_t first_sample,
                       uint32_t samples) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_ambient_device: samples is 0");
-    if (samples > kMaxAmbientSamples) return fail(ctx, RT_E_INVALID, "rt_ambient_device: samples above 16777216");
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_ambient_device", {{points_device, "points", 16, false}, {out_device, "out", 16, false}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_ambient(ctx, points_device, out_device, count, first_sample, samples);
+    return device_query(ctx, kAmbient, points_device, out_device, count, samples, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) {
+                            return run_ambient(ctx, in, out, n, first_sample, samples);
+                        });
 }
 
 int rt_ambient(rt_ctx* ctx, const rt_ambient_point* points, float* out, uint64_t count, uint32_t first_sample,
                uint32_t samples) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_ambient: samples is 0");
-    if (samples > kMaxAmbientSamples) return fail(ctx, RT_E_INVALID, "rt_ambient: samples above 16777216");
-    if (count == 0) return RT_OK;
-    if (!points || !out) return fail(ctx, RT_E_INVALID, "rt_ambient: points or out is NULL");
-    return staged_query(ctx, points, sizeof(rt_ambient_point), out, 16, count, false, nullptr,
-                        [&](const void* d_pts, void* d_out, uint64_t n) {
-                            return run_ambient(ctx, d_pts, d_out, n, first_sample, samples);
+    return staged_query(ctx, kAmbient, points, out, count, samples, nullptr,
+                        [=](const void* d_in, void* d_out, uint64_t n, unsigned long long*) {
+                            return run_ambient(ctx, d_in, d_out, n, first_sample, samples);
                         });
 }
 
@@ -2744,13 +2670,9 @@ int rt_ambient(rt_ctx* ctx, const rt_ambient_point* points, float* out, uint64_t
 static int run_probe_sh(rt_ctx* ctx, const void* probes, void* sh, uint64_t count, uint32_t bounces,
                         uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
     if (count == 0) return RT_OK;
-    if (bounces == 0) {  // the bounce loop does not run (:226): no light, no segments
-        RT_HIP(ctx, hipMemsetAsync(sh, 0, (size_t)count * 144u, ctx->stream));
-        return RT_OK;
-    }
+    if (bounces == 0) return answer_zero_bounces(ctx, sh, count, 144u);
     QueryLaunch q;
-    bool answered;
-    int rc = path_query_scene(ctx, nullptr, count, bounces, samples, kQueryProbe, q, &answered);
+    int rc = path_query_scene(ctx, count, bounces, samples, kQueryProbe, q);
     if (rc) return rc;
     // whole probes per launch: at most max("probe_chunk", samples) <= 2^26 items, 16 B each
     const uint64_t chunk = std::min<uint64_t>(count, std::max<uint32_t>(1u, ctx->probe_chunk / samples));
@@ -2802,34 +2724,19 @@ static int run_probe_sh(rt_ctx* ctx, const void* probes, void* sh, uint64_t coun
     return RT_OK;
 }
 
+constexpr QueryFamily kProbeSh = {"rt_probe_sh", "rt_probe_sh_device", "probes", "sh", sizeof(rt_probe),
+                                  144, 16, kMaxProbeSamples, true};
+
 int rt_probe_sh_device(rt_ctx* ctx, const void* probes_device, void* sh_device, uint64_t count, uint32_t bounces,
                        uint32_t first_sample, uint32_t samples, void* segments_device) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_probe_sh_device: samples is 0");
-    if (samples > kMaxProbeSamples) return fail(ctx, RT_E_INVALID, "rt_probe_sh_device: samples above 16777216");
-    if (count == 0) return RT_OK;
-    int rc = check_device_ptrs(ctx, "rt_probe_sh_device", {{probes_device, "probes", 16, false},
-                                                           {sh_device, "sh", 16, false},
-                                                           {segments_device, "segments", 8, true}});
-    if (rc || (rc = query_enter(ctx))) return rc;
-    return run_probe_sh(ctx, probes_device, sh_device, count, bounces, first_sample, samples,
-                        static_cast<unsigned long long*>(segments_device));
+    return device_query(ctx, kProbeSh, probes_device, sh_device, count, samples, segments_device,
+                        bind_path_run(run_probe_sh, ctx, bounces, first_sample, samples));
 }
 
 int rt_probe_sh(rt_ctx* ctx, const rt_probe* probes, float* sh, uint64_t count, uint32_t bounces, uint32_t first_sample,
                 uint32_t samples, uint64_t* segments) {
-    RT_ENTER_NOFLUSH(ctx);
-    if (samples == 0) return fail(ctx, RT_E_INVALID, "rt_probe_sh: samples is 0");
-    if (samples > kMaxProbeSamples) return fail(ctx, RT_E_INVALID, "rt_probe_sh: samples above 16777216");
-    if (count == 0) {
-        if (segments) *segments = 0;
-        return RT_OK;
-    }
-    if (!probes || !sh) return fail(ctx, RT_E_INVALID, "rt_probe_sh: probes or sh is NULL");
-    return staged_query(ctx, probes, sizeof(rt_probe), sh, 144, count, true, segments,
-                        [&](const void* d_probes, void* d_sh, uint64_t n) {
-                            return run_probe_sh(ctx, d_probes, d_sh, n, bounces, first_sample, samples, ctx->d_radiance_segs);
-                        });
+    return staged_query(ctx, kProbeSh, probes, sh, count, samples, segments,
+                        bind_path_run(run_probe_sh, ctx, bounces, first_sample, samples));
 }
 
 int rt_read_output(rt_ctx* ctx, uint32_t* out) {

@@ -1,0 +1,121 @@
+// rt_launch.h — what the translation units of the library call in one another: the kernel
+// launchers and launch queries that the .hip files define for rt_abi.cpp, and rt_abi.cpp's
+// rt_set_global_error. Every file that defines one of these includes this header, so a signature
+// that drifts is seen where it is defined, and the library is linked with --no-undefined, so one
+// that is declared and called but nowhere defined fails the build.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "rt_kernel_args.h"
+#include "rt_query_schedule.h"
+#include "rt_scene_math.h"
+#include "sphere_bvh.h"
+#include "tri_cone.h"
+#include "tri_qnode.h"
+
+// rt_abi.cpp: the last error of a call without a context, rt_last_error(NULL)
+void rt_set_global_error(const std::string& msg);
+
+// pathtrace.hip
+hipError_t rt_launch_math_selftest(uint32_t which, unsigned long long* mismatches, uint32_t* first_bad,
+                                   hipStream_t stream);
+hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
+                               size_t lds_bytes, uint32_t blocks, hipStream_t stream);
+hipError_t rt_pathtrace_pick_config(int mode, bool tris, bool frame_par, size_t lds_bytes,
+                                    size_t lds_bytes_per_thread, uint32_t force_threads, uint32_t waves_cap,
+                                    uint32_t* threads, int* blocks_per_cu);
+hipError_t rt_launch_primary(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, uint32_t threads,
+                             uint32_t min_waves, hipStream_t stream);
+hipError_t rt_launch_brute_wf(const KernelArgs& ka, bool tris, bool scalar_stream, size_t lds_bytes, uint32_t blocks,
+                              hipStream_t stream);
+size_t rt_brute_wf_tile_bytes(bool scalar_stream);
+uint32_t rt_brute_wf_chunk();
+hipError_t rt_launch_resolve(float4* accum, uint32_t* output, const float4* light, uint32_t width, uint32_t height,
+                             uint32_t tiles_x, uint32_t owned_tiles, uint32_t rank, uint32_t world, uint32_t k0,
+                             uint32_t samples, uint32_t frames, unsigned long long* clock, hipStream_t stream);
+hipError_t rt_launch_pack_output(uint32_t* output, uint32_t* packed, uint32_t width, uint32_t height, uint32_t tiles_x,
+                                 uint32_t n_tiles, uint32_t first_rank, uint32_t ranks, uint32_t world,
+                                 uint64_t stride_px, uint32_t skip_rank, bool unpack, hipStream_t stream);
+hipError_t rt_launch_pack(const float4* accum, float4* dst, uint32_t width, uint32_t height, uint32_t tiles_x,
+                          uint32_t owned_tiles, uint32_t rank, uint32_t world, hipStream_t stream);
+hipError_t rt_launch_unpack(const float4* src, float4* accum, uint32_t* output, uint32_t width, uint32_t height,
+                            uint32_t tiles_x, uint32_t n_tiles, uint32_t first_rank, uint32_t ranks, uint32_t world,
+                            uint64_t stride_px, uint32_t skip_rank, float divisor, hipStream_t stream);
+
+// scene_edit.hip
+hipError_t rt_launch_edit(const float* model, const uint32_t* tri_object, const uint32_t* sub_object,
+                          const uint2* object_tris, const rt_scene::Placement* place, uint32_t object_count,
+                          uint32_t n_tri, uint32_t n_sub, RtTriangleHot* tris, float4* bounds, RtSubObject* subs,
+                          RtObject* objects, hipStream_t stream);
+hipError_t rt_launch_quantize_tri_nodes(const SphereBvhNode* nodes, uint32_t n, const uint32_t* src,
+                                        const uint32_t* skip, uint32_t n_out, SphereBvhNode* out32, uint4* q,
+                                        float4* grid, hipStream_t stream);
+hipError_t rt_launch_refit(SphereBvhNode* nodes, const SubObjectPrim* prims, const RtSubObject* subs,
+                           const uint32_t* order, const uint32_t* level_offsets, uint32_t n_levels, float* extent_out,
+                           hipStream_t stream);
+hipError_t rt_launch_tri_leafcert(const SubObjectPrim* prims, uint32_t n_prims, const RtSubObject* subs,
+                                  const RtTriangleHot* tris, uint32_t n_tri, TriLeafCert* out, hipStream_t stream);
+hipError_t rt_launch_tri_leaftris(const SubObjectPrim* prims, uint32_t n_prims, const RtTriangleHot* tris,
+                                  uint32_t n_tri, uint4* out, hipStream_t stream);
+
+// the query kernels (query.hip, occlusion.hip, radiance.hip, ambient.hip): per kernel the workgroup size of a
+// placement, the resident workgroups per CU, and the launch on a schedule of rt_query_schedule.h
+uint32_t rt_query_threads(int mode, bool tris);
+hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_query(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                           const void* rays, void* hits, uint64_t count, unsigned long long* counter,
+                           hipStream_t stream);
+hipError_t rt_launch_pick_ray(const KernelArgs& ka, uint32_t x, uint32_t y, void* ray_out, hipStream_t stream);
+uint32_t rt_occlusion_threads(int mode, bool tris);
+hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                               const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
+                               hipStream_t stream);
+uint32_t rt_radiance_threads(int mode, bool tris);
+hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_radiance(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                              const void* rays, void* radiance, uint64_t count, unsigned long long* counter,
+                              unsigned long long* segments, uint32_t first_sample, uint32_t samples, uint32_t stripes,
+                              hipStream_t stream);
+hipError_t rt_launch_gather_resolve(const void* partials, void* radiance, uint32_t points, uint32_t stripes,
+                                    hipStream_t stream);
+hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                                 const void* probes, void* lights, uint64_t count, unsigned long long* counter,
+                                 unsigned long long* segments, uint32_t first_sample, uint32_t samples,
+                                 hipStream_t stream);
+hipError_t rt_launch_probe_resolve(const void* lights, const void* probes, void* sh, uint32_t count, uint32_t first_sample,
+                                   uint32_t samples, hipStream_t stream);
+uint32_t rt_ambient_threads(int mode, bool tris);
+hipError_t rt_ambient_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                             const void* points, void* partials, uint64_t count, unsigned long long* counter,
+                             uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
+
+// denoise.hip
+hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
+hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
+                                     const void* hits, float4* plane_a, float4* plane_b, hipStream_t stream);
+hipError_t rt_launch_denoise_init(const float4* accum, float4* dst, uint32_t* packed, uint64_t n, float div,
+                                  hipStream_t stream);
+hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
+                                  uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
+                                  float sigma_depth, bool lds, hipStream_t stream, const float4* nn = nullptr);
+hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
+                              float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
+                              uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
+                              hipStream_t stream);
+
+// display.hip
+hipError_t rt_launch_display_meter(const float4* src, uint64_t n, float div, uint32_t* bins, hipStream_t stream);
+hipError_t rt_launch_display_solve(uint32_t* bins, uint32_t* kept, uint32_t* state, uint32_t low_permille,
+                                   uint32_t high_permille, float key, float min_exposure, float max_exposure,
+                                   float adaptation, bool has_state, hipStream_t stream);
+hipError_t rt_launch_display_tone(const float4* src, uint32_t* dst, uint64_t n, float div, const uint32_t* state,
+                                  float exposure, float iw2, const float* srgb, uint32_t op, uint32_t encode,
+                                  hipStream_t stream);

@@ -30,8 +30,7 @@
 #include <vector>
 
 #include "rt_abi.h"
-
-void rt_set_global_error(const std::string& msg);  // rt_abi.cpp: rt_last_error(NULL)
+#include "rt_launch.h"
 
 namespace {
 

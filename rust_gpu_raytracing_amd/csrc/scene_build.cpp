@@ -16,9 +16,8 @@
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_launch.h"
 #include "rt_scene_math.h"
-
-void rt_set_global_error(const std::string& msg);
 
 namespace {
 

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "rt_kernel_args.h"
+#include "rt_launch.h"
 #include "rt_scene_math.h"
 #include "sphere_bvh.h"
 #include "tri_cone.h"

@@ -279,7 +279,7 @@ class Renderer:
         trip, stream-ordered on the context's stream -- and returns a CUDA (n, 16) int32
         tensor of rt_hit records."""
         if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
-            return self._trace_rays_device(rays)
+            return self._device_query("rt_trace_rays_device", rays, 8, "rays", (16,), "int32", call_empty=False)
         rays = np.asarray(rays)
         if rays.dtype != B.QUERY_RAY:
             r = np.ascontiguousarray(rays, np.float32)
@@ -293,29 +293,77 @@ class Renderer:
         self._call("rt_trace_rays", N.ptr(rays), N.ptr(hits), rays.shape[0])
         return hits
 
-    def _trace_rays_device(self, rays):
+    def _device_query(self, entry, records, columns, noun, out_shape, out_dtype, scalars=(), segments=None,
+                      call_empty=True):
+        """The device form of a query, ``entry``: ``records``, a CUDA float32 tensor of shape
+        (n, ``columns``) that the messages call ``noun``, answered into a new (n, *``out_shape``)
+        tensor of the torch dtype named ``out_dtype``. ``scalars`` follow the count in the call.
+        ``segments``: None for an entry without a segments argument, else whether to count them (a
+        null pointer if not); counted, (out, segments) comes back. Without ``call_empty`` an empty
+        batch returns before the call, else the call is made with null record pointers."""
         import torch
 
-        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
-        if rays.device.index != self.device:
-            raise ValueError("device rays must live on the renderer's device")
-        rays = rays.contiguous()
-        hits = torch.empty((rays.shape[0], 16), dtype=torch.int32, device=rays.device)
-        if rays.shape[0] == 0:
-            return hits
+        if not records.is_cuda or records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != columns:
+            raise ValueError(f"device {noun} must be a CUDA float32 tensor of shape (n, {columns})")
+        if records.device.index != self.device:
+            raise ValueError(f"device {noun} must live on the renderer's device")
+        records = records.contiguous()
+        n = records.shape[0]
+        out = torch.empty((n, *out_shape), dtype=getattr(torch, out_dtype), device=records.device)
+        if n == 0 and not call_empty:
+            return out
+        counter = torch.zeros(1, dtype=torch.int64, device=records.device) if segments else None
+        args = [ctypes.c_void_p(records.data_ptr() if n else None), ctypes.c_void_p(out.data_ptr() if n else None), n,
+                *scalars]
+        if segments is not None:
+            args.append(ctypes.c_void_p(counter.data_ptr()) if segments else None)
         # the query runs on the context's stream: order it after the tensor's producers,
         # and the caller's stream after it
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
-        cur = torch.cuda.current_stream(rays.device)
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=records.device)
+        cur = torch.cuda.current_stream(records.device)
         mine.wait_stream(cur)
-        self._call("rt_trace_rays_device", ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(hits.data_ptr()),
-                   rays.shape[0])
+        self._call(entry, *args)
         # (no record_stream on the context's stream: the caller's stream, which owns both tensors,
         # is ordered after the query here, and the context's stream may be destroyed -- close() --
         # before the tensors are freed)
         cur.wait_stream(mine)
-        return hits
+        return (out, int(counter.item())) if segments else out
+
+    @staticmethod
+    def _t_max_column(t_max, n):
+        """``t_max``, a scalar or an (n,) array, as what a record array's t_max field takes."""
+        bound = np.asarray(t_max, np.float32)
+        if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != n):
+            raise ValueError("t_max must be a scalar or an (n,) array")
+        return bound
+
+    @staticmethod
+    def _pack_records(values, name, fields, noun, first_stream, streams, t_max=None):
+        """The flat record array of a query with RNG streams, of the dtype ``name`` of ``buffers``:
+        ``values`` as it is if it has that dtype (``streams`` must then be None), else an
+        (n, 3 * len(fields)) float32 array whose columns fill ``fields`` three at a time, with
+        ``streams`` (default: ``first_stream`` + the record's position in the batch) and, for
+        records that have one, ``t_max``."""
+        dtype = getattr(B, name)
+        values = np.asarray(values)
+        if values.dtype == dtype:
+            if streams is not None:
+                raise ValueError(f"{name} records carry their own stream" + (" and t_max" if "t_max" in dtype.names else ""))
+        else:
+            r = np.ascontiguousarray(values, np.float32)
+            if r.ndim != 2 or r.shape[1] != 3 * len(fields):
+                article = "an" if name[0] in "AEIOU" else "a"
+                raise ValueError(f"{noun} must be (n, {3 * len(fields)}) float32 or {article} {name} array")
+            values = np.zeros(r.shape[0], dtype)
+            for i, field in enumerate(fields):
+                values[field] = r[:, 3 * i:3 * i + 3]
+            s = first_stream + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
+            if s.shape != (r.shape[0],):
+                raise ValueError("streams must be an (n,) array")
+            values["stream"] = s
+            if "t_max" in dtype.names:
+                values["t_max"] = Renderer._t_max_column(t_max, r.shape[0])
+        return np.ascontiguousarray(values.reshape(-1))
 
     def pick(self, x: int, y: int) -> np.ndarray:
         """The closest hit of pixel (x, y)'s un-jittered camera ray (rt_pick): one ``buffers.HIT``."""
@@ -338,7 +386,7 @@ class Renderer:
         if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
             if t_max is not None:
                 raise ValueError("device rays carry t_max in their last column")
-            return self._occluded_device(rays)
+            return self._device_query("rt_occluded_device", rays, 8, "rays", (), "uint8", call_empty=False)
         rays = np.asarray(rays)
         if rays.dtype == B.OCCLUSION_RAY:
             if t_max is not None:
@@ -353,33 +401,10 @@ class Renderer:
             if r.shape[1] == 7:
                 rays["t_max"] = r[:, 6]
             else:
-                bound = np.asarray(np.inf if t_max is None else t_max, np.float32)
-                if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != r.shape[0]):
-                    raise ValueError("t_max must be a scalar or an (n,) array")
-                rays["t_max"] = bound
+                rays["t_max"] = self._t_max_column(np.inf if t_max is None else t_max, r.shape[0])
         rays = np.ascontiguousarray(rays.reshape(-1))
         out = np.zeros(rays.shape[0], np.uint8)
         self._call("rt_occluded", N.ptr(rays), N.ptr(out), rays.shape[0])
-        return out
-
-    def _occluded_device(self, rays):
-        import torch
-
-        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
-        if rays.device.index != self.device:
-            raise ValueError("device rays must live on the renderer's device")
-        rays = rays.contiguous()
-        out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
-        if rays.shape[0] == 0:
-            return out
-        # the stream handshake of _trace_rays_device
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
-        cur = torch.cuda.current_stream(rays.device)
-        mine.wait_stream(cur)
-        self._call("rt_occluded_device", ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                   rays.shape[0])
-        cur.wait_stream(mine)
         return out
 
     def occluded_segments(self, a, b):
@@ -415,48 +440,14 @@ class Renderer:
         if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
             if streams is not None:
                 raise ValueError("device rays carry their stream in column 3")
-            return self._radiance_device(rays, bounces, first_sample, samples, return_segments)
-        rays = np.asarray(rays)
-        if rays.dtype == B.RADIANCE_RAY:
-            if streams is not None:
-                raise ValueError("RADIANCE_RAY records carry their own stream")
-        else:
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] != 6:
-                raise ValueError("rays must be (n, 6) float32 or a RADIANCE_RAY array")
-            rays = np.zeros(r.shape[0], B.RADIANCE_RAY)
-            rays["origin"] = r[:, :3]
-            rays["direction"] = r[:, 3:]
-            s = np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
-            if s.shape != (r.shape[0],):
-                raise ValueError("streams must be an (n,) array")
-            rays["stream"] = s
-        rays = np.ascontiguousarray(rays.reshape(-1))
+            return self._device_query("rt_radiance_device", rays, 8, "rays", (4,), "float32",
+                                      (int(bounces), int(first_sample), int(samples)), bool(return_segments))
+        rays = self._pack_records(rays, "RADIANCE_RAY", ("origin", "direction"), "rays", 0, streams)
         out = np.zeros((rays.shape[0], 4), np.float32)
         segments = ctypes.c_uint64(0)
         self._call("rt_radiance", N.ptr(rays), N.ptr(out), rays.shape[0], int(bounces), int(first_sample),
                    int(samples), ctypes.byref(segments))
         return (out, segments.value) if return_segments else out
-
-    def _radiance_device(self, rays, bounces, first_sample, samples, return_segments):
-        import torch
-
-        if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
-        if rays.device.index != self.device:
-            raise ValueError("device rays must live on the renderer's device")
-        rays = rays.contiguous()
-        out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
-        segments = torch.zeros(1, dtype=torch.int64, device=rays.device) if return_segments else None
-        # the stream handshake of _trace_rays_device
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
-        cur = torch.cuda.current_stream(rays.device)
-        mine.wait_stream(cur)
-        self._call("rt_radiance_device", ctypes.c_void_p(rays.data_ptr() if rays.shape[0] else None),
-                   ctypes.c_void_p(out.data_ptr() if rays.shape[0] else None), rays.shape[0], int(bounces),
-                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
-        cur.wait_stream(mine)
-        return (out, int(segments.item())) if return_segments else out
 
     # ------------------------------------------------------------------ gather queries
     def gather(self, points, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,
@@ -479,48 +470,14 @@ class Renderer:
         if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
             if streams is not None:
                 raise ValueError("device points carry their stream in column 3")
-            return self._gather_device(points, bounces, first_sample, samples, return_segments)
-        points = np.asarray(points)
-        if points.dtype == B.GATHER_POINT:
-            if streams is not None:
-                raise ValueError("GATHER_POINT records carry their own stream")
-        else:
-            r = np.ascontiguousarray(points, np.float32)
-            if r.ndim != 2 or r.shape[1] != 6:
-                raise ValueError("points must be (n, 6) float32 or a GATHER_POINT array")
-            points = np.zeros(r.shape[0], B.GATHER_POINT)
-            points["position"] = r[:, :3]
-            points["normal"] = r[:, 3:]
-            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
-            if s.shape != (r.shape[0],):
-                raise ValueError("streams must be an (n,) array")
-            points["stream"] = s
-        points = np.ascontiguousarray(points.reshape(-1))
+            return self._device_query("rt_gather_device", points, 8, "points", (4,), "float32",
+                                      (int(bounces), int(first_sample), int(samples)), bool(return_segments))
+        points = self._pack_records(points, "GATHER_POINT", ("position", "normal"), "points", 1, streams)
         out = np.zeros((points.shape[0], 4), np.float32)
         segments = ctypes.c_uint64(0)
         self._call("rt_gather", N.ptr(points), N.ptr(out), points.shape[0], int(bounces), int(first_sample),
                    int(samples), ctypes.byref(segments))
         return (out, segments.value) if return_segments else out
-
-    def _gather_device(self, points, bounces, first_sample, samples, return_segments):
-        import torch
-
-        if not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
-            raise ValueError("device points must be a CUDA float32 tensor of shape (n, 8)")
-        if points.device.index != self.device:
-            raise ValueError("device points must live on the renderer's device")
-        points = points.contiguous()
-        out = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-        segments = torch.zeros(1, dtype=torch.int64, device=points.device) if return_segments else None
-        # the stream handshake of _trace_rays_device
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=points.device)
-        cur = torch.cuda.current_stream(points.device)
-        mine.wait_stream(cur)
-        self._call("rt_gather_device", ctypes.c_void_p(points.data_ptr() if points.shape[0] else None),
-                   ctypes.c_void_p(out.data_ptr() if points.shape[0] else None), points.shape[0], int(bounces),
-                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
-        cur.wait_stream(mine)
-        return (out, int(segments.item())) if return_segments else out
 
     # ------------------------------------------------------------------ ambient queries
     def ambient(self, points, streams=None, t_max=np.inf, samples: int = 64, first_sample: int = 1,
@@ -545,26 +502,7 @@ class Renderer:
             if streams is not None:
                 raise ValueError("device points carry their stream in column 3 and t_max in column 7")
             return self._ambient_device(points, first_sample, samples)
-        points = np.asarray(points)
-        if points.dtype == B.AMBIENT_POINT:
-            if streams is not None:
-                raise ValueError("AMBIENT_POINT records carry their own stream and t_max")
-        else:
-            r = np.ascontiguousarray(points, np.float32)
-            if r.ndim != 2 or r.shape[1] != 6:
-                raise ValueError("points must be (n, 6) float32 or an AMBIENT_POINT array")
-            points = np.zeros(r.shape[0], B.AMBIENT_POINT)
-            points["position"] = r[:, :3]
-            points["normal"] = r[:, 3:]
-            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
-            if s.shape != (r.shape[0],):
-                raise ValueError("streams must be an (n,) array")
-            points["stream"] = s
-            bound = np.asarray(t_max, np.float32)
-            if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != r.shape[0]):
-                raise ValueError("t_max must be a scalar or an (n,) array")
-            points["t_max"] = bound
-        points = np.ascontiguousarray(points.reshape(-1))
+        points = self._pack_records(points, "AMBIENT_POINT", ("position", "normal"), "points", 1, streams, t_max)
         if device:
             import torch
 
@@ -575,22 +513,8 @@ class Renderer:
         return out[:, :3].copy(), out[:, 3].copy()
 
     def _ambient_device(self, points, first_sample, samples):
-        import torch
-
-        if not points.is_cuda or points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 8:
-            raise ValueError("device points must be a CUDA float32 tensor of shape (n, 8)")
-        if points.device.index != self.device:
-            raise ValueError("device points must live on the renderer's device")
-        points = points.contiguous()
-        out = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
-        # the stream handshake of _trace_rays_device
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=points.device)
-        cur = torch.cuda.current_stream(points.device)
-        mine.wait_stream(cur)
-        self._call("rt_ambient_device", ctypes.c_void_p(points.data_ptr() if points.shape[0] else None),
-                   ctypes.c_void_p(out.data_ptr() if points.shape[0] else None), points.shape[0], int(first_sample),
-                   int(samples))
-        cur.wait_stream(mine)
+        out = self._device_query("rt_ambient_device", points, 8, "points", (4,), "float32",
+                                 (int(first_sample), int(samples)))
         return out[:, :3], out[:, 3]
 
     # ------------------------------------------------------------------ probe queries
@@ -614,47 +538,14 @@ class Renderer:
         if not isinstance(positions, np.ndarray) and hasattr(positions, "is_cuda"):
             if streams is not None:
                 raise ValueError("device probes carry their stream in column 3")
-            return self._probe_sh_device(positions, bounces, first_sample, samples, return_segments)
-        probes = np.asarray(positions)
-        if probes.dtype == B.PROBE:
-            if streams is not None:
-                raise ValueError("PROBE records carry their own stream")
-        else:
-            r = np.ascontiguousarray(probes, np.float32)
-            if r.ndim != 2 or r.shape[1] != 3:
-                raise ValueError("positions must be (n, 3) float32 or a PROBE array")
-            probes = np.zeros(r.shape[0], B.PROBE)
-            probes["position"] = r
-            s = 1 + np.arange(r.shape[0], dtype=np.uint32) if streams is None else np.asarray(streams, np.uint32)
-            if s.shape != (r.shape[0],):
-                raise ValueError("streams must be an (n,) array")
-            probes["stream"] = s
-        probes = np.ascontiguousarray(probes.reshape(-1))
+            return self._device_query("rt_probe_sh_device", positions, 4, "probes", (9, 4), "float32",
+                                      (int(bounces), int(first_sample), int(samples)), bool(return_segments))
+        probes = self._pack_records(positions, "PROBE", ("position",), "positions", 1, streams)
         out = np.zeros((probes.shape[0], 9, 4), np.float32)
         segments = ctypes.c_uint64(0)
         self._call("rt_probe_sh", N.ptr(probes), N.ptr(out), probes.shape[0], int(bounces), int(first_sample),
                    int(samples), ctypes.byref(segments))
         return (out, segments.value) if return_segments else out
-
-    def _probe_sh_device(self, probes, bounces, first_sample, samples, return_segments):
-        import torch
-
-        if not probes.is_cuda or probes.dtype != torch.float32 or probes.dim() != 2 or probes.shape[1] != 4:
-            raise ValueError("device probes must be a CUDA float32 tensor of shape (n, 4)")
-        if probes.device.index != self.device:
-            raise ValueError("device probes must live on the renderer's device")
-        probes = probes.contiguous()
-        out = torch.empty((probes.shape[0], 9, 4), dtype=torch.float32, device=probes.device)
-        segments = torch.zeros(1, dtype=torch.int64, device=probes.device) if return_segments else None
-        # the stream handshake of _trace_rays_device
-        mine = torch.cuda.ExternalStream(self.stream_handle, device=probes.device)
-        cur = torch.cuda.current_stream(probes.device)
-        mine.wait_stream(cur)
-        self._call("rt_probe_sh_device", ctypes.c_void_p(probes.data_ptr() if probes.shape[0] else None),
-                   ctypes.c_void_p(out.data_ptr() if probes.shape[0] else None), probes.shape[0], int(bounces),
-                   int(first_sample), int(samples), ctypes.c_void_p(segments.data_ptr()) if return_segments else None)
-        cur.wait_stream(mine)
-        return (out, int(segments.item())) if return_segments else out
 
     # ------------------------------------------------------------------ feature buffers & denoiser
     def compute_features(self) -> None:
@@ -793,7 +684,7 @@ class Renderer:
         plane = plane.contiguous()
         p.source = N.RT_DISPLAY_PLANE
         # the transform runs on the context's stream: order it after the tensor's producers, and the
-        # caller's stream after it (as _trace_rays_device does)
+        # caller's stream after it (as _device_query does)
         mine = torch.cuda.ExternalStream(self.stream_handle, device=plane.device)
         cur = torch.cuda.current_stream(plane.device)
         mine.wait_stream(cur)
