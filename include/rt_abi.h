@@ -1245,7 +1245,10 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
 
 /* Exact variants of the launch schedule and of the acceleration structures (new, ABI 12;
  * they were environment variables read at rt_create up to ABI 11), for A/B measurements:
- * every setting renders the same bits as the default. Takes effect from the next launch.
+ * every setting renders the same bits as the default. Takes effect from the next launch,
+ * at any point of a context's life: frames queued before the call are launched under the
+ * setting they were queued with. The key "tile_schedule" is rt_set_tile_schedule (it discards
+ * the recorded costs and orders too).
  * Keys and values (default first):
  *   "scene_in_lds" 1|0, "lds_mode" 2|1|0 (highest LDS staging mode), "block_threads"
  *   0|256|512|1024 (0: by occupancy), "waves_per_cu" 0..32 (0: 16), "trav_threshold" 0..63

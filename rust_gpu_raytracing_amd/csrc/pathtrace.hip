@@ -73,8 +73,9 @@ constexpr uint32_t kPrimaryThreads = 1024;  // default: 16 units per workgroup, 
 // Claims stay dynamic, so expensive tiles still balance across waves. The
 // counters start at zero: each launch zeroes the other half of the
 // double-buffered counter array for the next launch (stream order makes that
-// visible). Lane 0 does the memory operations; results are wave-uniform.
-constexpr uint32_t kQueueStride = 64;  // u32 between stripe counters (256 B)
+// visible) -- all kQueueStripesMax stripes of it, since the next launch may run
+// with another stripe count (rt_kernel_args.h). Lane 0 does the memory
+// operations; results are wave-uniform.
 
 // The cost-ordered schedule's device state (KernelArgs::sched).
 __device__ __forceinline__ uint32_t* sched_orders(const KernelArgs& ka) { return ka.sched + 2u * ka.owned_tiles; }
@@ -527,7 +528,8 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
     const unsigned long long wave_t0 = realtime();
     unsigned long long wave_dry = 0;  // when the queue first came up empty for this wave
 #endif
-    if (blockIdx.x == 0 && threadIdx.x < ka.queue_stripes) ka.queue_next[threadIdx.x * kQueueStride] = 0u;
+    static_assert(kThreads >= kQueueStripesMax, "one thread per stripe counter");
+    if (blockIdx.x == 0 && threadIdx.x < kQueueStripesMax) ka.queue_next[threadIdx.x * kQueueStride] = 0u;
     // home stripe: this XCD's (blocks are dealt round-robin over the XCDs, so
     // blockIdx / 8 spreads an XCD's blocks over its stripes when there are more)
     TileQueue queue{(xcc_id() + 8u * (blockIdx.x >> 3)) % ka.queue_stripes, 0u};

@@ -70,13 +70,11 @@ constexpr size_t kDiagWaveRecords = 2 * 65536;
 constexpr size_t kCounterWords = 1 + kDiagCounters + kDiagWaveRecords;
 // Tile queue: counters per stripe (pathtrace.hip, claim_tile), 256 B apart;
 // kQueueStripes = 4 per XCD by default (measured: C2 0.599 ms at 8, 0.595 at 32; C1
-// 0.076 -> 0.058 ms), up to kQueueStripesMax (RT_QUEUE_STRIPES).
+// 0.076 -> 0.058 ms), up to kQueueStripesMax (rt_kernel_args.h, with kQueueStride).
 constexpr uint32_t kQueueStripes = 32;
 // Triangle-walk distance pruning: a node is skipped once its (inflated) box
 // is entered beyond best * (1 + kTriPruneRho) + kTriPruneAbs * (|o| + extent) / |d|.
 constexpr float kTriPruneRho = 1.0f / 64.0f;
-constexpr uint32_t kQueueStripesMax = 64;
-constexpr uint32_t kQueueStride = 64;
 // A wave goes back to shading once at most this many of its 64 lanes are still
 // traversing (pathtrace.hip, step 4 of the kernel loop). The longer a trace is
 // against a shading pass, the earlier it pays to shade the finished lanes
@@ -213,7 +211,7 @@ struct rt_ctx {
     uint32_t* d_out = nullptr;
     unsigned long long* d_counter = nullptr;
     uint32_t* d_queue = nullptr;  // [stream][2] x kQueueStripesMax tile-queue counters, kQueueStride apart
-    uint32_t queue_parity[2] = {0, 0};  // per stream: which half its next launch uses (the launch zeroes the other)
+    uint32_t queue_parity[2] = {0, 0};  // per stream: which half its next launch uses (the launch zeroes all of the other)
     uint32_t queue_stripes = kQueueStripes;  // tuning "queue_stripes"
     int n_cu = 0;
     bool force_global_scene = false;   // tuning "scene_in_lds" 0
@@ -2942,6 +2940,18 @@ int rt_streamed_bytes_l2(rt_ctx* ctx, uint64_t* out) {
     return RT_OK;
 }
 
+// rt_set_tile_schedule and the tuning key "tile_schedule": the claim order, with the recorded costs
+// and orders of both streams discarded (after RT_ENTER: the primary stream follows the auxiliary one).
+static int set_tile_schedule(rt_ctx* ctx, uint32_t schedule) {
+    ctx->tile_schedule = schedule;
+    for (int si = 0; si < 2; si++) {
+        if (ctx->d_tile_sched[si])
+            RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_sched[si], 0, (4 * (size_t)ctx->owned_tiles + 2) * 4, ctx->stream));
+        ctx->sched_launches[si] = 0;
+    }
+    return RT_OK;
+}
+
 // Exact variants of the schedule and the acceleration structures, for A/B measurements (the
 // product reads no environment): every setting renders the same bits.
 int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
@@ -3017,7 +3027,7 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
     } else if (k == "leaf_batch") {
         if ((rc = range(0, 8)) == RT_OK) ctx->leaf_batch = (uint32_t)v;
     } else if (k == "tile_schedule") {
-        if ((rc = range(0, 1)) == RT_OK) ctx->tile_schedule = (uint32_t)v;
+        if ((rc = range(0, 1)) == RT_OK) rc = set_tile_schedule(ctx, (uint32_t)v);
     } else if (k == "frame_parallel") {
         rc = flag(ctx->frame_parallel);
     } else if (k == "batch_overlap") {
@@ -3051,13 +3061,7 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
 int rt_set_tile_schedule(rt_ctx* ctx, uint32_t schedule) {
     RT_ENTER(ctx);
     if (schedule > 1) return fail(ctx, RT_E_INVALID, "tile schedule must be 0 (index order) or 1 (cost-ordered)");
-    ctx->tile_schedule = schedule;
-    for (int si = 0; si < 2; si++) {
-        if (ctx->d_tile_sched[si])
-            RT_HIP(ctx, hipMemsetAsync(ctx->d_tile_sched[si], 0, (4 * (size_t)ctx->owned_tiles + 2) * 4, ctx->stream));
-        ctx->sched_launches[si] = 0;
-    }
-    return RT_OK;
+    return set_tile_schedule(ctx, schedule);
 }
 
 int rt_tile_schedule_state(rt_ctx* ctx, uint32_t* order, uint32_t* costs) {

@@ -100,6 +100,13 @@ constexpr uint32_t kLeafTriSlots = 8;                       // triangle slots pe
 constexpr uint32_t kLeafTriWords = 3 * kLeafTriSlots;       // uint4 per block (384 B)
 constexpr uint32_t kLeafBatchWaveBytes = 64 * 48;
 
+// Tile queue (pathtrace.hip, claim_tile): one counter per stripe, kQueueStride u32 (256 B) apart, at
+// most kQueueStripesMax stripes (tuning "queue_stripes"). A half of the double-buffered counter
+// array is kQueueStripesMax * kQueueStride words; every launch zeroes all of the other half, so a
+// launch finds its counters at zero whatever stripe counts the launches before it ran with.
+constexpr uint32_t kQueueStripesMax = 64;
+constexpr uint32_t kQueueStride = 64;
+
 // Diagnostic counters ahead of the per-wave records in KernelArgs::diag
 // (RT_DIAG: words 0-29; RT_DIAG_TAIL: words 0-7, then 2 words per wave from here).
 constexpr uint32_t kDiagHeaderWords = 32;
