@@ -56,7 +56,9 @@ extern "C" {
  * 12, additive: display transform (rt_display, rt_read_display, rt_copy_display_to_device,
  * rt_display_state, rt_display_reset, rt_display_default_params, rt_display_params);
  * 12, additive: probe queries (rt_probe_sh, rt_probe_sh_device, rt_probe);
- * 12, additive: ambient queries (rt_ambient, rt_ambient_device, rt_ambient_point). */
+ * 12, additive: ambient queries (rt_ambient, rt_ambient_device, rt_ambient_point);
+ * 12, additive: motion records for the temporal denoiser (rt_denoise_temporal_motion, rt_motion,
+ * rt_motion_from_transforms, rt_read_feature_ids, rt_feature_ids_device). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -817,6 +819,13 @@ RT_API int rt_ambient_device(rt_ctx* ctx, const void* points_device, void* out_d
  * rt_features_device: the planes' device pointers (computed if stale, stream-ordered on
  *   rt_stream(ctx)); valid until rt_destroy, rewritten by the next recomputation.
  *
+ * THE ID PLANE. A third plane of width*height uint2, row-major, resolved from the same record as
+ * the two planes above: id.x = rt_hit.kind and id.y = rt_hit.index (the object index of a triangle
+ * hit, the sphere index as uploaded of a sphere hit); a miss is (0, 0). It is allocated with the
+ * other planes and falls under the same scene-epoch rule.
+ * rt_read_feature_ids: synchronous (computes the planes if stale); width*height*2 uint32.
+ * rt_feature_ids_device: the plane's device pointer, like rt_features_device.
+ *
  * THE FILTER. The arithmetic below is the contract.
  *
  * Everything is f32, one IEEE operation per written operation, in the written order.
@@ -904,6 +913,8 @@ RT_API int rt_denoise_default_params(rt_denoise_params* out); /* {4, 1.0f, 0.1f,
 RT_API int rt_compute_features(rt_ctx* ctx);
 RT_API int rt_read_features(rt_ctx* ctx, float* normal_depth, float* albedo_hit);
 RT_API int rt_features_device(rt_ctx* ctx, const void** normal_depth, const void** albedo_hit);
+RT_API int rt_read_feature_ids(rt_ctx* ctx, uint32_t* ids /* 2 per pixel: kind, index */);
+RT_API int rt_feature_ids_device(rt_ctx* ctx, const void** ids);
 RT_API int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
 RT_API int rt_read_denoised(rt_ctx* ctx, uint32_t* rgba8_out, float* rgba_f32_out);
 RT_API int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t bytes_per_row);
@@ -926,8 +937,9 @@ RT_API int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t by
  * previous stays what it was (possibly none) and the current slot is overwritten. Within one
  * accumulation generation the history is therefore always the last result of the generation before
  * it -- the past is never counted twice -- and the growing accumulation outweighs it as N grows.
- * rt_temporal_reset invalidates both slots: call it after material, texture or geometry edits,
- * which reprojection cannot validate.
+ * rt_temporal_reset invalidates both slots: call it after texture or lighting edits, and after a
+ * material edit that is not marked RT_MOTION_DROP, which reprojection cannot validate. Object and
+ * sphere motion no longer need a reset: rt_denoise_temporal_motion (below) follows them.
  *
  * world_to_pixel is the CURRENT camera's map from world space to pixel coordinates (pixel (x, y) is
  * where the un-jittered ray of pixel (x, y) lands); it is stored with the slot and used by the next
@@ -1003,7 +1015,9 @@ RT_API int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device, uint32_t by
  * Errors: those of rt_denoise, plus RT_E_INVALID for a NULL rt_temporal_params (the matrix has no
  * default), a non-finite matrix entry, max_history outside 1..65536, sigma_position not finite or
  * <= 0, normal_min not finite or outside [-1, 1]. A failing call leaves the history as it was.
- * rt_temporal_reset: drops all history; RT_OK when there is none.
+ * rt_temporal_reset: drops all history; RT_OK when there is none. Needed after texture and lighting
+ *   edits and after material edits not marked RT_MOTION_DROP; not after object or sphere motion
+ *   that rt_denoise_temporal_motion is told about.
  * rt_read_temporal: synchronous; the pre-filter blend `out` (width*height*4 floats) and the per-pixel
  *   history length n_out (width*height floats) of the last call; either pointer may be NULL.
  *   RT_E_INVALID before any rt_denoise_temporal and after rt_temporal_reset. */
@@ -1530,6 +1544,90 @@ RT_API int rt_scene_object_update(const float* normalized_points, uint32_t trian
  * before the next frame: no host round trip. Asynchronous. */
 RT_API int rt_set_object_models(rt_ctx* ctx, const float* normalized_points, uint32_t triangle_count);
 RT_API int rt_update_objects(rt_ctx* ctx, const rt_object_transform* transforms, uint32_t count);
+
+/* ---- motion records for the temporal denoiser (ABI 12, additive: motion records) ----
+ *
+ * rt_denoise_temporal reprojects every pixel as if its surface stood still, so a piece the user
+ * drags is rejected by the position test and shows a fresh 1-spp estimate on every edit.
+ * rt_denoise_temporal_motion takes, per object and per sphere, how that primitive moved since the
+ * previous call, reprojects each surface point through its own primitive's motion and validates
+ * history against the primitive's identity (the ID plane of the feature buffers).
+ *
+ * A record says where the surface point that is NOW at X was at the previous call: A X, A = (L | t)
+ * a row-major 3x4. flags 0 is a static primitive (m and normal_scale are ignored); RT_MOTION_MOVED
+ * uses them; RT_MOTION_DROP gives the primitive's pixels no history (it appeared, teleported or
+ * changed material) and wins over MOVED. The records are an input to the contract, like
+ * world_to_pixel, not part of it.
+ *
+ * rt_motion_from_transforms (no context; errors through rt_last_error(NULL)): the records of
+ * `count` objects from their edit states at the previous and at the current call, for the pose
+ * update_triangles applies, world = Rz Ry Rx(rotation) p scale + transformation with the f32
+ * rotation matrix of rt_scene_object_update: L = (s_prev/s_cur) R_prev R_cur^T, t = T_prev - L T_cur,
+ * normal_scale = s_cur/s_prev, computed in double and rounded once to f32. A byte-identical pair
+ * gives flags 0. RT_E_INVALID: a NULL argument with count > 0, a scale not finite or <= 0.
+ *
+ * rt_denoise_temporal_motion: rt_denoise_temporal (same slots, generation rule, observation-point
+ * behaviour, errors and "changes nothing a render observes") under the motion contract below. The
+ * tables are copied before the call returns into a context-owned buffer that grows as needed and is
+ * freed by rt_destroy; a table may be NULL with count 0 (everything static). Indices are rt_hit.index:
+ * object i of the object buffer, sphere i as uploaded; a primitive beyond its table is static.
+ * Further RT_E_INVALID: a NULL table with count > 0, unknown flag bits, a non-finite m or
+ * normal_scale in a MOVED record. A failing call leaves the history as it was.
+ * STATE. Each slot gains an I plane (uint2, 8 B per pixel), allocated at the first motion call. A
+ * slot written by this entry point has ids, one written by rt_denoise_temporal has none (that call's
+ * kernel and memory traffic are as before). rt_read_temporal, rt_read_denoised,
+ * rt_copy_denoised_to_device and rt_temporal_reset serve both entry points.
+ *
+ * THE MOTION STAGE (rt_denoise_temporal_motion; tests/temporal_motion_ref.py restates it from here).
+ *
+ * This is the temporal contract above, word for word, with the changes below. Everything is f32, one
+ * IEEE operation per written operation, in the written order, with no contraction.
+ *
+ * 2m. Record lookup.
+ *   id_p comes from the ID plane.
+ *   The record R is objects[id.y] if id.x == 2 && id.y < object_count.
+ *   R is spheres[id.y] if id.x == 1 && id.y < sphere_count.
+ *   Otherwise there is no record. Misses never have one.
+ *   X_p is as in step 2.
+ *   If R has DROP, the pixel has no history.
+ *   If R has MOVED, for i = 0..2:
+ *     Y_i = ((m[4i]*X.x + m[4i+1]*X.y) + m[4i+2]*X.z) + m[4i+3];
+ *     g_i = ((m[4i]*n.x + m[4i+1]*n.y) + m[4i+2]*n.z) * normal_scale.
+ *   Otherwise Y = X_p and g = n_p, chosen by selection. The pixel does no arithmetic.
+ *
+ * 3m. Projection. Step 3 projects Y instead of X_p.
+ *
+ * 4m. Tap tests.
+ *   The tap tests are those of step 4, with g in the normal test and e = Y - X_q in the position test.
+ *   f = X_p - o and r2 are unchanged. The tolerance scales with the current distance.
+ *   On a hit, and only when the previous slot has an I plane, one further test applies: both words of
+ *   I_q equal id_p.
+ *
+ * 7m. Store. Store as step 7: X = (X_p, hit_p) and Nn = (n_p, n_out). In addition I = id_p.
+ *
+ * Steps 1, 5, 6 and 8 are unchanged.
+ * End of the motion contract. */
+#define RT_MOTION_MOVED 1u /* use m and normal_scale */
+#define RT_MOTION_DROP 2u  /* this primitive takes no history (appeared, teleported, re-materialed) */
+typedef struct rt_motion {
+    float m[12];           /* row-major 3x4 A: where the surface point now at X was at the previous call */
+    float normal_scale;    /* n' = (L n) * normal_scale, L the 3x3 part of A */
+    uint32_t flags;        /* 0: static. Other bits than MOVED and DROP: RT_E_INVALID */
+    uint32_t _reserved[2]; /* 0 */
+} rt_motion;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_motion) == 64, "rt_motion is 64 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_motion) == 64, "rt_motion is 64 bytes");
+#endif
+
+RT_API int rt_motion_from_transforms(const rt_object_transform* prev, const rt_object_transform* cur, uint32_t count,
+                                     rt_motion* out);
+RT_API int rt_denoise_temporal_motion(rt_ctx* ctx, const rt_temporal_params* params,
+                                      const rt_denoise_params* denoise_params /* NULL: defaults */,
+                                      const rt_motion* objects, uint32_t object_count, const rt_motion* spheres,
+                                      uint32_t sphere_count);
 
 /* Readback of the scene geometry the kernel sees (after host or device
  * updates). Triangles come back as full 112-byte records. Synchronous. */

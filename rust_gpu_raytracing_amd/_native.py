@@ -124,6 +124,19 @@ class rt_temporal_params(ctypes.Structure):
                 ("sigma_position", ctypes.c_float), ("normal_min", ctypes.c_float), ("_reserved", ctypes.c_uint32)]
 
 
+class rt_object_transform(ctypes.Structure):
+    _fields_ = [("rotation", ctypes.c_float * 3), ("scale", ctypes.c_float),
+                ("transformation", ctypes.c_float * 3), ("_padding", ctypes.c_uint32)]
+
+
+RT_MOTION_MOVED, RT_MOTION_DROP = 1, 2
+
+
+class rt_motion(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_float * 12), ("normal_scale", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("_reserved", ctypes.c_uint32 * 2)]
+
+
 class rt_display_params(ctypes.Structure):
     _fields_ = [("source", ctypes.c_uint32), ("tone_operator", ctypes.c_uint32), ("encode", ctypes.c_uint32),
                 ("auto_exposure", ctypes.c_uint32), ("exposure", ctypes.c_float), ("key", ctypes.c_float),
@@ -134,6 +147,7 @@ class rt_display_params(ctypes.Structure):
 assert ctypes.sizeof(rt_params) == 48
 assert ctypes.sizeof(rt_display_params) == 48
 assert ctypes.sizeof(rt_temporal_params) == 80
+assert ctypes.sizeof(rt_object_transform) == 32 and ctypes.sizeof(rt_motion) == 64
 assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
@@ -198,6 +212,11 @@ SIGNATURES = {
     "rt_temporal_default_params": (ctypes.c_int, [ctypes.POINTER(rt_temporal_params)]),
     "rt_denoise_temporal": (ctypes.c_int, [_P, ctypes.POINTER(rt_temporal_params), ctypes.POINTER(rt_denoise_params)]),
     "rt_temporal_reset": (ctypes.c_int, [_P]),
+    "rt_read_feature_ids": (ctypes.c_int, [_P, _P]),
+    "rt_feature_ids_device": (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    "rt_motion_from_transforms": (ctypes.c_int, [_P, _P, _U32, _P]),
+    "rt_denoise_temporal_motion": (ctypes.c_int, [_P, ctypes.POINTER(rt_temporal_params),
+                                                  ctypes.POINTER(rt_denoise_params), _P, _U32, _P, _U32]),
     "rt_read_temporal": (ctypes.c_int, [_P, _P, _P]),
     "rt_display_default_params": (ctypes.c_int, [ctypes.POINTER(rt_display_params)]),
     "rt_display": (ctypes.c_int, [_P, ctypes.POINTER(rt_display_params), _P]),

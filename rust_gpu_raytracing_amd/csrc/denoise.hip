@@ -1,6 +1,6 @@
 // denoise.hip -- first-hit feature buffers, the guided a-trous filter and its temporal
-// reprojection stage for gfx950 (rt_compute_features, rt_denoise, rt_denoise_temporal; DESIGN.md
-// §5.4d, §5.4f).
+// reprojection stage for gfx950 (rt_compute_features, rt_denoise, rt_denoise_temporal,
+// rt_denoise_temporal_motion).
 //
 // FEATURES. Two float4 planes of width*height pixels, row-major:
 //   plane A: normal.xyz, t          plane B: albedo.rgb, hit (1.0f or 0.0f)
@@ -149,6 +149,44 @@
 // fall into a few rows -- and 48 B written to the current slot. The two slots are distinct buffers:
 // no hazard, no atomics. The four taps' loads are issued together (indices clamped into the image)
 // and the invalid ones dropped with selects, never multiplied by zero.
+//
+// THE MOTION STAGE (rt_denoise_temporal_motion; tests/temporal_motion_ref.py restates it from here).
+//
+// This is the temporal contract above, word for word, with the changes below. Everything is f32, one
+// IEEE operation per written operation, in the written order, with no contraction.
+//
+// 2m. Record lookup.
+//   id_p comes from the ID plane.
+//   The record R is objects[id.y] if id.x == 2 && id.y < object_count.
+//   R is spheres[id.y] if id.x == 1 && id.y < sphere_count.
+//   Otherwise there is no record. Misses never have one.
+//   X_p is as in step 2.
+//   If R has DROP, the pixel has no history.
+//   If R has MOVED, for i = 0..2:
+//     Y_i = ((m[4i]*X.x + m[4i+1]*X.y) + m[4i+2]*X.z) + m[4i+3];
+//     g_i = ((m[4i]*n.x + m[4i+1]*n.y) + m[4i+2]*n.z) * normal_scale.
+//   Otherwise Y = X_p and g = n_p, chosen by selection. The pixel does no arithmetic.
+//
+// 3m. Projection. Step 3 projects Y instead of X_p.
+//
+// 4m. Tap tests.
+//   The tap tests are those of step 4, with g in the normal test and e = Y - X_q in the position test.
+//   f = X_p - o and r2 are unchanged. The tolerance scales with the current distance.
+//   On a hit, and only when the previous slot has an I plane, one further test applies: both words of
+//   I_q equal id_p.
+//
+// 7m. Store. Store as step 7: X = (X_p, hit_p) and Nn = (n_p, n_out). In addition I = id_p.
+//
+// Steps 1, 5, 6 and 8 are unchanged.
+// End of the motion contract.
+//
+// The motion instance (kMotion) of the temporal kernel adds, per pixel: 8 B of ID plane, one guarded
+// 64-B record gather (four 16-B loads; neighbouring pixels share ids, so the lanes of a wave mostly
+// read one and the same record), 4 x 8 B of I taps issued with the other tap loads (indices clamped,
+// dropped by selects) and 8 B of I written. The instances without it compile to the code they had
+// before it existed (profiles/temporal_motion/kernel_regs.txt).
+// The ID plane: rt_feature_resolve_kernel stores (rt_hit.kind, rt_hit.index) of the record planes A
+// and B are resolved from, (0, 0) on a miss: one extra 8-B store per pixel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -189,19 +227,22 @@ __global__ void __launch_bounds__(256) rt_feature_rays_kernel(KernelArgs ka, uin
     rays[2 * (size_t)i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
 }
 
-// rt_hit records of pixels [first, first + count) -> the two feature planes.
+// rt_hit records of pixels [first, first + count) -> the two feature planes and the ID plane.
 __global__ void __launch_bounds__(256) rt_feature_resolve_kernel(KernelArgs ka, uint32_t first, uint32_t count,
                                                                  const float4* __restrict__ rays,
                                                                  const uint4* __restrict__ hits,
                                                                  float4* __restrict__ plane_a,
-                                                                 float4* __restrict__ plane_b) {
+                                                                 float4* __restrict__ plane_b,
+                                                                 uint2* __restrict__ plane_i) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
     const uint4 q0 = hits[4 * (size_t)i], q1 = hits[4 * (size_t)i + 1], q2 = hits[4 * (size_t)i + 2];
     const float t = __uint_as_float(q0.x);
     const uint32_t kind = q2.w;
     float4 a, b;
+    uint2 id = make_uint2(0u, 0u);
     if (kind != 0u) {
+        id = make_uint2(kind, reinterpret_cast<const uint32_t*>(hits)[16 * (size_t)i + 12]);  // rt_hit.index
         const float u = __uint_as_float(q1.w), v = __uint_as_float(q2.x);
         const uint32_t mi = min(q2.y, ka.material_count - 1u);
         const f4 c = decode_texel(fetch_texture(ka, ka.materials[mi].texture_index, u, v), ka.srgb);
@@ -215,6 +256,7 @@ __global__ void __launch_bounds__(256) rt_feature_resolve_kernel(KernelArgs ka, 
     }
     plane_a[(size_t)first + i] = a;
     plane_b[(size_t)first + i] = b;
+    plane_i[(size_t)first + i] = id;
 }
 
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays,
@@ -226,10 +268,11 @@ hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t
 }
 
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
-                                     const void* hits, float4* plane_a, float4* plane_b, hipStream_t stream) {
+                                     const void* hits, float4* plane_a, float4* plane_b, uint2* plane_i,
+                                     hipStream_t stream) {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_feature_resolve_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, ka, first, count,
-                       static_cast<const float4*>(rays), static_cast<const uint4*>(hits), plane_a, plane_b);
+                       static_cast<const float4*>(rays), static_cast<const uint4*>(hits), plane_a, plane_b, plane_i);
     return hipGetLastError();
 }
 
@@ -425,11 +468,36 @@ struct TemporalArgs {
     float m[16];                        // the previous slot's world_to_pixel
     float n;                            // N = D
     float max_history, sigma2, normal_min;  // (float)max_history, sigma_position*sigma_position
+    // kMotion (rt_denoise_temporal_motion) only; the plain instances never read past this line
+    const uint2* __restrict__ ids;      // the ID plane: rt_hit.kind, rt_hit.index
+    const uint2* __restrict__ prev_i;   // the previous slot's I plane; null: that slot has no ids
+    uint2* __restrict__ cur_i;          // the current slot's I plane
+    const float4* __restrict__ objects; // motion records, four float4 each: m[0..3], m[4..7], m[8..11],
+    const float4* __restrict__ spheres; //   (normal_scale, flags, 0, 0)
+    uint32_t object_count, sphere_count;
 };
 
+namespace {
+
+// Step 2m: the motion record of the primitive (kind, index), or a static one (flags 0) where the
+// tables have none. The index is used only behind its bounds test.
+__device__ __forceinline__ void load_motion(const TemporalArgs& t, uint32_t kind, uint32_t index, float4 (&r)[4]) {
+    const bool obj = kind == 2u && index < t.object_count, sph = kind == 1u && index < t.sphere_count;
+    r[0] = r[1] = r[2] = r[3] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (obj || sph) {
+        const float4* __restrict__ rec = (obj ? t.objects : t.spheres) + 4u * (size_t)index;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = rec[k];
+    }
+}
+
+}  // namespace
+
 // Steps 1-7 of the temporal contract. kGen: the camera ray is computed from the matrices
-// (rt_update_camera_matrices in effect); else it is read from the ray buffer.
-template <bool kGen>
+// (rt_update_camera_matrices in effect); else it is read from the ray buffer. kMotion: the motion
+// contract's steps 2m, 3m, 4m and 7m (rt_denoise_temporal_motion); the instances without it hold
+// none of that code.
+template <bool kGen, bool kMotion>
 __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, TemporalArgs t) {
     const uint32_t tid = threadIdx.x;
     const uint32_t x = blockIdx.x * kTileW + (tid & (kTileW - 1u)), y = blockIdx.y * kTileH + tid / kTileW;
@@ -461,11 +529,33 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
     const f3 xp = hit ? mk(o.x + d.x * nd.w, o.y + d.y * nd.w, o.z + d.z * nd.w) : d;
     float4 out = c;
     float n_out = t.n;
-    if (t.prev_c) {
+    // 2m. the record of this pixel's primitive: yp and g are X_p and n_p carried to the previous call
+    f3 yp = xp, g = mk(nd.x, nd.y, nd.z);
+    uint2 id = make_uint2(0u, 0u);
+    bool keep = true;
+    if constexpr (kMotion) {
+        id = t.ids[idx];
+        // neighbouring pixels share ids: the lanes of a wave mostly gather one and the same 64 B
+        float4 r[4];
+        load_motion(t, id.x, id.y, r);
+        const uint32_t flags = __float_as_uint(r[3].y);
+        const float ns = r[3].x;
+        const f3 ym = mk(((r[0].x * xp.x + r[0].y * xp.y) + r[0].z * xp.z) + r[0].w,
+                         ((r[1].x * xp.x + r[1].y * xp.y) + r[1].z * xp.z) + r[1].w,
+                         ((r[2].x * xp.x + r[2].y * xp.y) + r[2].z * xp.z) + r[2].w);
+        const f3 gm = mk(((r[0].x * nd.x + r[0].y * nd.y) + r[0].z * nd.z) * ns,
+                         ((r[1].x * nd.x + r[1].y * nd.y) + r[1].z * nd.z) * ns,
+                         ((r[2].x * nd.x + r[2].y * nd.y) + r[2].z * nd.z) * ns);
+        const bool moved = (flags & 1u) != 0u;
+        yp = mk(moved ? ym.x : xp.x, moved ? ym.y : xp.y, moved ? ym.z : xp.z);  // per component: registers
+        g = mk(moved ? gm.x : nd.x, moved ? gm.y : nd.y, moved ? gm.z : nd.z);
+        keep = (flags & 2u) == 0u;
+    }
+    if (t.prev_c && keep) {
         // 3. projection
-        float c0 = (t.m[0] * xp.x + t.m[4] * xp.y) + t.m[8] * xp.z;
-        float c1 = (t.m[1] * xp.x + t.m[5] * xp.y) + t.m[9] * xp.z;
-        float c3 = (t.m[3] * xp.x + t.m[7] * xp.y) + t.m[11] * xp.z;
+        float c0 = (t.m[0] * yp.x + t.m[4] * yp.y) + t.m[8] * yp.z;
+        float c1 = (t.m[1] * yp.x + t.m[5] * yp.y) + t.m[9] * yp.z;
+        float c3 = (t.m[3] * yp.x + t.m[7] * yp.y) + t.m[11] * yp.z;
         if (hit) {
             c0 = c0 + t.m[12];
             c1 = c1 + t.m[13];
@@ -480,7 +570,10 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
             const int ix = (int)x0, iy = (int)y0;
             const float wt[4] = {bx * by, ax * by, bx * ay, ax * ay};
             float4 qc[4], qx[4], qn[4];
+            uint2 qid[4];
             bool inside[4];
+            bool with_ids = false;
+            if constexpr (kMotion) with_ids = t.prev_i != nullptr;  // uniform: a kernel argument
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int qxi = ix + (k & 1), qyi = iy + (k >> 1);
@@ -490,6 +583,10 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
                 qc[k] = ld_f4(t.prev_c, qi);
                 qx[k] = ld_f4(t.prev_x, qi);
                 qn[k] = ld_f4(t.prev_nn, qi);
+                if constexpr (kMotion) {
+                    qid[k] = make_uint2(id.x, id.y);  // a slot without ids hands back id itself
+                    if (with_ids) qid[k] = t.prev_i[qi];
+                }
             }
             const float fx_ = xp.x - o.x, fy_ = xp.y - o.y, fz_ = xp.z - o.z;
             const float r2 = (fx_ * fx_ + fy_ * fy_) + fz_ * fz_;
@@ -500,10 +597,12 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
             for (int k = 0; k < 4; ++k) {
                 bool ok = inside[k] && wt[k] > 0.0f && qx[k].w == hit_p;
                 if (hit) {
-                    const float dn = (nd.x * qn[k].x + nd.y * qn[k].y) + nd.z * qn[k].z;
-                    const float ex = xp.x - qx[k].x, ey = xp.y - qx[k].y, ez = xp.z - qx[k].z;
+                    const float dn = (g.x * qn[k].x + g.y * qn[k].y) + g.z * qn[k].z;
+                    const float ex = yp.x - qx[k].x, ey = yp.y - qx[k].y, ez = yp.z - qx[k].z;
                     const float e2 = (ex * ex + ey * ey) + ez * ez;
                     ok = ok && dn >= t.normal_min && e2 <= lim;
+                    // 4m. a slot without ids hands back id itself
+                    if constexpr (kMotion) ok = ok && qid[k].x == id.x && qid[k].y == id.y;
                 }
                 // 5. history sums
                 sw = ok ? sw + wt[k] : sw;
@@ -530,6 +629,7 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
     t.cur_c[idx] = out;
     t.cur_x[idx] = make_float4(xp.x, xp.y, xp.z, hit_p);
     t.cur_nn[idx] = make_float4(nd.x, nd.y, nd.z, n_out);
+    if constexpr (kMotion) t.cur_i[idx] = id;
     if (t.dn) {
         t.dn[idx] = out;
         t.packed[idx] = pack_rgba8(clamp01(out.x), clamp01(out.y), clamp01(out.z), clamp01(out.w));
@@ -539,7 +639,7 @@ __global__ void __launch_bounds__(kThreads) rt_temporal_kernel(KernelArgs ka, Te
 hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
                               float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
                               uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
-                              hipStream_t stream) {
+                              hipStream_t stream, const TemporalMotion* motion) {
     TemporalArgs t{};
     t.accum = accum;
     t.nd = nd;
@@ -560,9 +660,22 @@ hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const f
     t.sigma2 = sigma2;
     t.normal_min = normal_min;
     const dim3 grid((ka.width + kTileW - 1u) / kTileW, (ka.height + kTileH - 1u) / kTileH);
-    if (ka.gen_rays)
-        hipLaunchKernelGGL(rt_temporal_kernel<true>, grid, dim3(kThreads), 0, stream, ka, t);
-    else
-        hipLaunchKernelGGL(rt_temporal_kernel<false>, grid, dim3(kThreads), 0, stream, ka, t);
+    if (motion) {  // rt_denoise_temporal_motion
+        t.ids = motion->ids;
+        t.prev_i = prev ? motion->prev_i : nullptr;
+        t.cur_i = motion->cur_i;
+        t.objects = motion->objects;
+        t.spheres = motion->spheres;
+        t.object_count = motion->object_count;
+        t.sphere_count = motion->sphere_count;
+        if (ka.gen_rays)
+            hipLaunchKernelGGL((rt_temporal_kernel<true, true>), grid, dim3(kThreads), 0, stream, ka, t);
+        else
+            hipLaunchKernelGGL((rt_temporal_kernel<false, true>), grid, dim3(kThreads), 0, stream, ka, t);
+    } else if (ka.gen_rays) {
+        hipLaunchKernelGGL((rt_temporal_kernel<true, false>), grid, dim3(kThreads), 0, stream, ka, t);
+    } else {
+        hipLaunchKernelGGL((rt_temporal_kernel<false, false>), grid, dim3(kThreads), 0, stream, ka, t);
+    }
     return hipGetLastError();
 }

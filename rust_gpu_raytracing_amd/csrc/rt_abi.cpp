@@ -18,6 +18,7 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rt_abi.h"
@@ -41,6 +42,7 @@ static_assert(sizeof(rt_query_ray) == 32, "rt_query_ray is two 16-B loads");
 static_assert(sizeof(rt_hit) == 64, "rt_hit is four 16-B stores");
 static_assert(sizeof(rt_denoise_params) == 16, "rt_denoise_params is 16 bytes");
 static_assert(sizeof(rt_temporal_params) == 80, "rt_temporal_params is 80 bytes");
+static_assert(sizeof(rt_motion) == 64 && offsetof(rt_motion, normal_scale) == 48, "rt_motion is four 16-B rows");
 static_assert(sizeof(rt_display_params) == 48, "rt_display_params is 48 bytes");
 static_assert(sizeof(rt_occlusion_ray) == sizeof(rt_query_ray), "rt_occlusion_ray is an rt_query_ray with t_max for _pad1");
 static_assert(sizeof(rt_radiance_ray) == sizeof(rt_query_ray), "rt_radiance_ray is an rt_query_ray with the stream for _pad0");
@@ -406,6 +408,7 @@ struct rt_ctx {
     uint64_t scene_epoch = 1;
     uint64_t feat_epoch = 0;                      // 0: never built
     float4* d_feat[2] = {};                       // plane A: normal.xyz, t; plane B: albedo.rgb, hit
+    uint2* d_feat_ids = nullptr;                  // the ID plane: rt_hit.kind, rt_hit.index
     void* d_feat_scratch = nullptr;               // one band's rays, then its records
     size_t feat_scratch_bytes = 0;
     uint32_t feature_band = kDefaultFeatureBand;  // tuning "feature_band": pixels per band
@@ -421,7 +424,11 @@ struct rt_ctx {
         float matrix[16] = {};
         uint64_t gen = 0;
         bool valid = false;
+        uint2* ids = nullptr;   // the I plane, allocated at the first rt_denoise_temporal_motion
+        bool has_ids = false;   // the call that wrote this slot wrote ids too
     } t_slot[2];
+    void* d_motion = nullptr;   // rt_denoise_temporal_motion: the object records, then the sphere records
+    size_t motion_bytes = 0;
     int t_cur = 0;            // the slot the last rt_denoise_temporal wrote (when valid)
     int t_prev = -1;          // the slot it read; -1: none
     uint64_t accum_gen = 0;   // G
@@ -932,7 +939,8 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out, ctx->d_disp_out, ctx->d_disp_meter,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
-                    ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2]};
+                    ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2],
+                    ctx->d_feat_ids, ctx->t_slot[0].ids, ctx->t_slot[1].ids, ctx->d_motion};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -2117,6 +2125,7 @@ static int build_features(rt_ctx* ctx) {
     if (rc) return rc;
     for (float4*& plane : ctx->d_feat)
         if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    if (!ctx->d_feat_ids && (rc = dev_alloc(ctx, &ctx->d_feat_ids, ctx->n_pixels))) return rc;
     const uint64_t band = std::min<uint64_t>(ctx->n_pixels, ctx->feature_band);
     if ((rc = grow_buffer(ctx, &ctx->d_feat_scratch, &ctx->feat_scratch_bytes,
                           band * (sizeof(rt_query_ray) + sizeof(rt_hit)))))
@@ -2131,7 +2140,7 @@ static int build_features(rt_ctx* ctx) {
         RT_HIP(ctx, rt_launch_feature_rays(kb, (uint32_t)first, n, d_rays, ctx->stream));
         if ((rc = run_query(ctx, d_rays, d_hits, n))) return rc;
         RT_HIP(ctx, rt_launch_feature_resolve(kb, (uint32_t)first, n, d_rays, d_hits, ctx->d_feat[0], ctx->d_feat[1],
-                                              ctx->stream));
+                                              ctx->d_feat_ids, ctx->stream));
     }
     ctx->feat_epoch = ctx->scene_epoch;
     ctx->primary_dirty = true;
@@ -2162,6 +2171,25 @@ int rt_features_device(rt_ctx* ctx, const void** normal_depth, const void** albe
     if (rc) return rc;
     *normal_depth = ctx->d_feat[0];
     *albedo_hit = ctx->d_feat[1];
+    return RT_OK;
+}
+
+int rt_read_feature_ids(rt_ctx* ctx, uint32_t* ids) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!ids) return fail(ctx, RT_E_INVALID, "rt_read_feature_ids: NULL argument");
+    const int rc = build_features(ctx);
+    if (rc) return rc;
+    RT_HIP(ctx, hipMemcpyAsync(ids, ctx->d_feat_ids, ctx->n_pixels * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_feature_ids_device(rt_ctx* ctx, const void** ids) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (!ids) return fail(ctx, RT_E_INVALID, "rt_feature_ids_device: NULL argument");
+    const int rc = build_features(ctx);
+    if (rc) return rc;
+    *ids = ctx->d_feat_ids;
     return RT_OK;
 }
 
@@ -2240,33 +2268,57 @@ int rt_temporal_default_params(rt_temporal_params* out) {
     return RT_OK;
 }
 
-int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt_denoise_params* params) {
-    RT_ENTER(ctx);  // an observation point: the queued frames are launched first
+// The two motion tables of an rt_denoise_temporal_motion; null for a plain rt_denoise_temporal.
+struct MotionTables {
+    const rt_motion* objects;
+    uint32_t object_count;
+    const rt_motion* spheres;
+    uint32_t sphere_count;
+};
+
+// rt_denoise_temporal and rt_denoise_temporal_motion after RT_ENTER: every argument is checked
+// before the first allocation or launch, so a failing call leaves the history as it was.
+static int denoise_temporal(rt_ctx* ctx, const std::string& who, const rt_temporal_params* tparams,
+                            const rt_denoise_params* params, const MotionTables* mt) {
     rt_denoise_params dp;
     (void)rt_denoise_default_params(&dp);
     if (params) dp = *params;
     if (ctx->world > 1)
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: a rank context (world_size > 1) has no full frame");
+        return fail(ctx, RT_E_INVALID, who + "a rank context (world_size > 1) has no full frame");
     if (ctx->params.accumulate != 1u)
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: Params.accumulate != 1 never writes the accumulation");
+        return fail(ctx, RT_E_INVALID, who + "Params.accumulate != 1 never writes the accumulation");
     if (ctx->k - 1u == 0u || (ctx->k - 1u) * ctx->params.compute_per_frame == 0u)  // D would be 0
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: no frame since the last reset");
+        return fail(ctx, RT_E_INVALID, who + "no frame since the last reset");
     if (dp.iterations > kMaxDenoiseIterations)
         return fail(ctx, RT_E_INVALID,
-                    "rt_denoise_temporal: iterations must be <= " + std::to_string(kMaxDenoiseIterations));
+                    who + "iterations must be <= " + std::to_string(kMaxDenoiseIterations));
     for (float sgm : {dp.sigma_color, dp.sigma_albedo, dp.sigma_depth})
         if (!std::isfinite(sgm) || !(sgm > 0.0f))
-            return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: every sigma must be finite and > 0");
-    if (!tparams) return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: rt_temporal_params is NULL (the matrix has no default)");
+            return fail(ctx, RT_E_INVALID, who + "every sigma must be finite and > 0");
+    if (!tparams) return fail(ctx, RT_E_INVALID, who + "rt_temporal_params is NULL (the matrix has no default)");
     const rt_temporal_params tp = *tparams;
     for (float m : tp.world_to_pixel)
-        if (!std::isfinite(m)) return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: world_to_pixel is not finite");
+        if (!std::isfinite(m)) return fail(ctx, RT_E_INVALID, who + "world_to_pixel is not finite");
     if (tp.max_history < 1u || tp.max_history > 65536u)
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: max_history must be in 1..65536");
+        return fail(ctx, RT_E_INVALID, who + "max_history must be in 1..65536");
     if (!std::isfinite(tp.sigma_position) || !(tp.sigma_position > 0.0f))
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: sigma_position must be finite and > 0");
+        return fail(ctx, RT_E_INVALID, who + "sigma_position must be finite and > 0");
     if (!std::isfinite(tp.normal_min) || tp.normal_min < -1.0f || tp.normal_min > 1.0f)
-        return fail(ctx, RT_E_INVALID, "rt_denoise_temporal: normal_min must be in [-1, 1]");
+        return fail(ctx, RT_E_INVALID, who + "normal_min must be in [-1, 1]");
+    if (mt) {
+        for (const auto& [table, count] : {std::pair{mt->objects, mt->object_count}, std::pair{mt->spheres, mt->sphere_count}}) {
+            if (count && !table) return fail(ctx, RT_E_INVALID, who + "a motion table is NULL with a count > 0");
+            for (uint32_t i = 0; i < count; i++) {
+                const rt_motion& r = table[i];
+                if (r.flags & ~(RT_MOTION_MOVED | RT_MOTION_DROP))
+                    return fail(ctx, RT_E_INVALID, who + "unknown rt_motion flags");
+                if (!(r.flags & RT_MOTION_MOVED)) continue;
+                bool finite = std::isfinite(r.normal_scale);
+                for (float v : r.m) finite = finite && std::isfinite(v);
+                if (!finite) return fail(ctx, RT_E_INVALID, who + "a MOVED rt_motion record is not finite");
+            }
+        }
+    }
     int rc = build_features(ctx);
     if (rc) return rc;
     for (float4*& plane : ctx->d_dn)
@@ -2275,6 +2327,21 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt
     for (rt_ctx::TemporalSlot& slot : ctx->t_slot)
         for (float4*& plane : slot.plane)
             if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
+    if (mt) {
+        for (rt_ctx::TemporalSlot& slot : ctx->t_slot)
+            if (!slot.ids && (rc = dev_alloc(ctx, &slot.ids, ctx->n_pixels))) return rc;
+        // the records as the caller wrote them (64 B each: three rows of A, then normal_scale, flags),
+        // objects first; copied through the pinned staging area, so the caller's arrays are free on return
+        const size_t ob = (size_t)mt->object_count * sizeof(rt_motion), sb = (size_t)mt->sphere_count * sizeof(rt_motion);
+        if (ob + sb) {
+            if ((rc = grow_buffer(ctx, &ctx->d_motion, &ctx->motion_bytes, ob + sb))) return rc;
+            void* p;
+            if ((rc = staging(ctx, ob + sb, &p))) return rc;
+            if (ob) std::memcpy(p, mt->objects, ob);
+            if (sb) std::memcpy(static_cast<unsigned char*>(p) + ob, mt->spheres, sb);
+            if ((rc = staged_copy(ctx, ctx->d_motion, ob + sb))) return rc;
+        }
+    }
     // the slot rule: within one accumulation generation the history stays the last result of the
     // generation before it, so the past is never counted twice
     int cur = ctx->t_cur, prev = ctx->t_prev;
@@ -2291,15 +2358,28 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt
     scene_base_args(ctx, kb);
     kb.camera_rays = ctx->d_rays;
     const bool zero = dp.iterations == 0;
+    TemporalMotion tm{};
+    if (mt) {
+        const float4* records = static_cast<const float4*>(ctx->d_motion);
+        tm.ids = ctx->d_feat_ids;
+        tm.prev_i = has_prev && ctx->t_slot[prev].has_ids ? ctx->t_slot[prev].ids : nullptr;
+        tm.cur_i = sc.ids;
+        tm.objects = records;
+        tm.spheres = records ? records + 4u * (size_t)mt->object_count : nullptr;
+        tm.object_count = mt->object_count;
+        tm.sphere_count = mt->sphere_count;
+    }
     RT_HIP(ctx, rt_launch_temporal(kb, ctx->d_accum, ctx->d_feat[0], ctx->d_feat[1],
                                    has_prev ? ctx->t_slot[prev].plane : nullptr, sc.plane,
                                    has_prev ? ctx->t_slot[prev].matrix : nullptr, zero ? ctx->d_dn[0] : nullptr,
                                    zero ? ctx->d_dn_out : nullptr, (float)n_samples, (float)tp.max_history,
-                                   tp.sigma_position * tp.sigma_position, tp.normal_min, ctx->stream));
+                                   tp.sigma_position * tp.sigma_position, tp.normal_min, ctx->stream,
+                                   mt ? &tm : nullptr));
     // the current slot is being rewritten from here on: the bookkeeping follows the launch
     std::memcpy(sc.matrix, tp.world_to_pixel, sizeof(sc.matrix));
     sc.gen = ctx->accum_gen;
     sc.valid = true;
+    sc.has_ids = mt != nullptr;
     ctx->t_cur = cur;
     ctx->t_prev = has_prev ? prev : -1;
     const float k_a = 1.0f / (dp.sigma_albedo * dp.sigma_albedo);
@@ -2315,6 +2395,19 @@ int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt
     }
     ctx->dn_result = zero ? 0 : (int)((dp.iterations - 1u) & 1u);
     return RT_OK;
+}
+
+int rt_denoise_temporal(rt_ctx* ctx, const rt_temporal_params* tparams, const rt_denoise_params* params) {
+    RT_ENTER(ctx);  // an observation point: the queued frames are launched first
+    return denoise_temporal(ctx, "rt_denoise_temporal: ", tparams, params, nullptr);
+}
+
+int rt_denoise_temporal_motion(rt_ctx* ctx, const rt_temporal_params* tparams, const rt_denoise_params* params,
+                               const rt_motion* objects, uint32_t object_count, const rt_motion* spheres,
+                               uint32_t sphere_count) {
+    RT_ENTER(ctx);  // an observation point, like rt_denoise_temporal
+    const MotionTables mt{objects, object_count, spheres, sphere_count};
+    return denoise_temporal(ctx, "rt_denoise_temporal_motion: ", tparams, params, &mt);
 }
 
 int rt_temporal_reset(rt_ctx* ctx) {

@@ -100,16 +100,27 @@ hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t l
 // denoise.hip
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
-                                     const void* hits, float4* plane_a, float4* plane_b, hipStream_t stream);
+                                     const void* hits, float4* plane_a, float4* plane_b, uint2* plane_i,
+                                     hipStream_t stream);
 hipError_t rt_launch_denoise_init(const float4* accum, float4* dst, uint32_t* packed, uint64_t n, float div,
                                   hipStream_t stream);
 hipError_t rt_launch_denoise_pass(const float4* nd, const float4* ah, const float4* src, float4* dst, uint32_t* packed,
                                   uint32_t width, uint32_t height, uint32_t step, float k_a, float k_c,
                                   float sigma_depth, bool lds, hipStream_t stream, const float4* nn = nullptr);
+// What rt_denoise_temporal_motion adds to a temporal launch: the ID plane, the slots' I planes
+// (prev_i null: the previous slot was written without ids) and the motion tables, 64 B per record.
+struct TemporalMotion {
+    const uint2* ids;
+    const uint2* prev_i;
+    uint2* cur_i;
+    const float4* objects;
+    const float4* spheres;
+    uint32_t object_count, sphere_count;
+};
 hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const float4* nd, const float4* ah,
                               float4* const prev[3], float4* const cur[3], const float* prev_matrix, float4* dn,
                               uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
-                              hipStream_t stream);
+                              hipStream_t stream, const TemporalMotion* motion = nullptr);
 
 // display.hip
 hipError_t rt_launch_display_meter(const float4* src, uint64_t n, float div, uint32_t* bins, hipStream_t stream);

@@ -210,4 +210,40 @@ int rt_scene_object_update(const float* normalized_points, uint32_t triangle_cou
     return RT_OK;
 }
 
+// A = T_prev o T_cur^-1 for the pose update_triangles applies (world = R p s + T, R the f32 matrix of
+// rotation_matrix): L = (s_prev/s_cur) R_prev R_cur^T, t = T_prev - L T_cur, in double, rounded once.
+int rt_motion_from_transforms(const rt_object_transform* prev, const rt_object_transform* cur, uint32_t count,
+                              rt_motion* out) {
+    if (count && (!prev || !cur || !out)) return fail(RT_E_INVALID, "rt_motion_from_transforms: NULL argument");
+    for (uint32_t o = 0; o < count; o++)
+        for (const rt_object_transform* t : {&prev[o], &cur[o]})
+            if (!std::isfinite(t->scale) || !(t->scale > 0.0f))
+                return fail(RT_E_INVALID, "rt_motion_from_transforms: a scale is not finite or <= 0");
+    for (uint32_t o = 0; o < count; o++) {
+        rt_motion& r = out[o];
+        std::memset(&r, 0, sizeof(r));
+        r.m[0] = r.m[5] = r.m[10] = 1.0f;
+        r.normal_scale = 1.0f;
+        if (std::memcmp(&prev[o], &cur[o], sizeof(rt_object_transform)) == 0) continue;  // static: flags 0
+        float rp[9], rc[9];  // three columns each
+        rotation_matrix(prev[o].rotation, rp);
+        rotation_matrix(cur[o].rotation, rc);
+        const double k = (double)prev[o].scale / (double)cur[o].scale;
+        for (int i = 0; i < 3; i++) {
+            double l[3], ti = (double)prev[o].transformation[i];
+            for (int j = 0; j < 3; j++) {
+                l[j] = 0.0;
+                for (int c = 0; c < 3; c++) l[j] += (double)rp[3 * c + i] * (double)rc[3 * c + j];
+                l[j] *= k;
+                ti -= l[j] * (double)cur[o].transformation[j];
+                r.m[4 * i + j] = (float)l[j];
+            }
+            r.m[4 * i + 3] = (float)ti;
+        }
+        r.normal_scale = (float)((double)cur[o].scale / (double)prev[o].scale);
+        r.flags = RT_MOTION_MOVED;
+    }
+    return RT_OK;
+}
+
 }  // extern "C"

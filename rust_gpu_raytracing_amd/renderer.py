@@ -569,12 +569,49 @@ class Renderer:
         self._call("rt_features_device", ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
 
+    def feature_ids(self) -> np.ndarray:
+        """The ID plane of the feature buffers (rt_read_feature_ids): (H, W, 2) uint32, the ``kind``
+        and ``index`` of the record ``trace_rays`` returns for each pixel's un-jittered camera ray;
+        (0, 0) on a miss."""
+        ids = np.zeros((self.height, self.width, 2), np.uint32)
+        self._call("rt_read_feature_ids", N.ptr(ids))
+        return ids
+
+    def feature_ids_device(self):
+        """The device pointer of the ID plane (rt_feature_ids_device)."""
+        a = ctypes.c_void_p()
+        self._call("rt_feature_ids_device", ctypes.byref(a))
+        return a.value
+
     def denoise_temporal(self, world_to_pixel, max_history=None, sigma_position=None, normal_min=None,
                          **denoise_kwargs):
         """Temporal reprojection, then the guided a-trous filter (rt_denoise_temporal; the contract
         is in include/rt_abi.h). ``world_to_pixel`` is the current camera's column-major 4x4
         (``Camera.world_to_pixel()``); arguments left None take rt_temporal_default_params and
         ``denoise_kwargs`` are ``denoise``'s. Returns (rgba_f32 (H, W, 4), rgba8 (H, W) uint32)."""
+        t, p = self._temporal_params(world_to_pixel, max_history, sigma_position, normal_min, denoise_kwargs,
+                                     "denoise_temporal")
+        self._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
+        return self.read_denoised()
+
+    def denoise_temporal_motion(self, world_to_pixel, objects=None, spheres=None, **params):
+        """``denoise_temporal`` that follows moving objects and spheres (rt_denoise_temporal_motion;
+        the motion contract is in include/rt_abi.h). ``objects`` and ``spheres`` are ``motion.MOTION``
+        arrays indexed like ``scene.objects`` and ``scene.spheres`` (``motion.object_motion``,
+        ``motion.sphere_motion``); None or a short table leaves the rest static. ``params`` are
+        ``denoise_temporal``'s. Returns what ``denoise_temporal`` returns."""
+        from .motion import MOTION
+
+        t, p = self._temporal_params(world_to_pixel, params.pop("max_history", None), params.pop("sigma_position", None),
+                                     params.pop("normal_min", None), params, "denoise_temporal_motion")
+        tables = []
+        for table in (objects, spheres):
+            a = np.zeros(0, MOTION) if table is None else np.ascontiguousarray(table, MOTION).reshape(-1)
+            tables += [N.ptr(a) if a.shape[0] else None, a.shape[0]]
+        self._call("rt_denoise_temporal_motion", ctypes.byref(t), ctypes.byref(p), *tables)
+        return self.read_denoised()
+
+    def _temporal_params(self, world_to_pixel, max_history, sigma_position, normal_min, denoise_kwargs, who):
         t = N.rt_temporal_params()
         N.check(None, self._lib.rt_temporal_default_params(ctypes.byref(t)), self._lib)
         t.world_to_pixel[:] = [float(v) for v in np.asarray(world_to_pixel, np.float32).reshape(16)]
@@ -586,15 +623,15 @@ class Renderer:
         N.check(None, self._lib.rt_denoise_default_params(ctypes.byref(p)), self._lib)
         for key, value in denoise_kwargs.items():
             if key not in ("iterations", "sigma_color", "sigma_albedo", "sigma_depth"):
-                raise TypeError(f"denoise_temporal() got an unexpected keyword argument {key!r}")
+                raise TypeError(f"{who}() got an unexpected keyword argument {key!r}")
             if value is not None:
                 setattr(p, key, value)
-        self._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p))
-        return self.read_denoised()
+        return t, p
 
     def temporal_reset(self) -> None:
-        """Drop all reprojection history (rt_temporal_reset): after material, texture or geometry
-        edits, which reprojection cannot validate."""
+        """Drop all reprojection history (rt_temporal_reset): after texture or lighting edits, and
+        after a material edit not marked ``motion.DROP``, which reprojection cannot validate.
+        Object and sphere motion need none with ``denoise_temporal_motion``."""
         self._call("rt_temporal_reset")
 
     def read_temporal(self):

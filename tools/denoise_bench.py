@@ -27,6 +27,15 @@ to exceed. Beside each pass: its one-touch traffic floor -- 48 B read and 16 B w
 at the HBM peak bench.py's roofline uses -- and the fraction of it achieved. `--bench-line`: a
 file holding bench.py's JSON result line, whose ms_per_step (the C2 frame) each figure is also
 given as a ratio of. The record carries the library's build hash.
+
+`--motion [--parent-lib FILE]`: instead of the above, on c3_chess only, rt_denoise_temporal against
+rt_denoise_temporal_motion with one moved piece (iterations 0, the stage alone, and the default 4),
+every timed call reprojecting the same previous slot; with `--parent-lib` (a build of the parent
+commit, tools/build_at_commit.py) the plain call is also timed on that library in the same process,
+the series alternating over the rounds, on two contexts per library. The plain call of this commit
+has to sit within the spread of the parent's repeated runs (minimum to maximum over the rounds of
+both parent contexts); the record says whether it does. Default
+`--out` then: profiles/temporal_motion/bench.json.
 """
 import argparse
 import ctypes
@@ -45,7 +54,102 @@ from rust_gpu_raytracing_amd.scene import build_config  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # bench.py: MI355X HBM3E peak
 PASS_BYTES_PER_PIXEL = 48 + 16
 TEMPORAL_BYTES_PER_PIXEL = 16 + 32 + 48 + 48
+MOTION_BYTES_PER_PIXEL = TEMPORAL_BYTES_PER_PIXEL + 8 + 8 + 8  # the ID plane, the I taps once, the I plane written
 MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16
+
+
+def motion_case(args):
+    """--motion: plain rt_denoise_temporal (this build and, if given, the parent's) against
+    rt_denoise_temporal_motion with one moved piece."""
+    import torch
+
+    from rust_gpu_raytracing_amd import motion
+
+    assert torch.cuda.is_available(), "denoise_bench needs a HIP device"
+    dev = torch.device("cuda:0")
+    # two contexts per library: what differs between two contexts of one build (where their planes
+    # landed in memory, their place in the round) is part of the spread a difference has to exceed
+    libs = {"this": None}
+    if args.parent_lib:
+        parent = N.load_library(args.parent_lib)
+        libs.update({"parent": parent, "this_b": None, "parent_b": parent})
+    series, renderers = {}, []
+    for which, lib in libs.items():
+        for kind in (("plain", "motion") if which == "this" else ("plain",)):
+            scene, bounces = build_config("c3_chess", width=args.width, height=args.height)
+            r = Renderer(scene, lib=lib)
+            renderers.append(r)
+            stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+            t = N.rt_temporal_params()
+            r._lib.rt_temporal_default_params(ctypes.byref(t))
+            t.world_to_pixel[:] = [float(v) for v in scene.camera.world_to_pixel().reshape(16)]
+            for _ in range(args.frames):
+                r.compute_frame(bounces)
+            if kind == "motion":  # a first call, then the piece with the most pixels moves
+                r._call("rt_denoise_temporal_motion", ctypes.byref(t), None, None, 0, None, 0)
+                before = motion.snapshot(scene)
+                ids = r.feature_ids()
+                counts = np.bincount(ids[..., 1][ids[..., 0] == 2], minlength=34)[:33]
+                counts[0] = 0
+                piece = scene.objects[int(counts.argmax())]
+                piece.transformation = (np.asarray(piece.transformation, np.float32)
+                                        + np.float32([0.35, 0.0, -0.25])).astype(np.float32)
+                piece.rotation = np.float32([0.0, 25.0, 0.0])
+                piece.scale = np.float32(1.1)
+                r.update_scene(device=True)
+                records = motion.object_motion(before["objects"], motion.snapshot(scene)["objects"])
+            else:
+                r._call("rt_denoise_temporal", ctypes.byref(t), None)
+                r.reset_accumulation()
+                records = None
+            for _ in range(args.frames):
+                r.compute_frame(bounces)
+            for it in (0, 4):
+                p = N.rt_denoise_params()
+                r._lib.rt_denoise_default_params(ctypes.byref(p))
+                p.iterations = it
+                if records is None:
+                    fn = (lambda r=r, t=t, p=p: r._call("rt_denoise_temporal", ctypes.byref(t), ctypes.byref(p)))
+                else:
+                    fn = (lambda r=r, t=t, p=p, rec=records: r._call(
+                        "rt_denoise_temporal_motion", ctypes.byref(t), ctypes.byref(p), N.ptr(rec), rec.shape[0], None, 0))
+                series[f"{kind}_it{it}/{which}"] = (r, stream, fn)
+    for r, stream, fn in series.values():  # warm-up
+        fn()
+        r.synchronize()
+    kept = int((renderers[1].read_temporal()[1] > args.frames).sum())  # this build's motion renderer
+    ms = {k: [] for k in series}
+    for _ in range(args.rounds):
+        for name, (r, stream, fn) in series.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            for _ in range(args.reps):
+                fn()
+            t1.record(stream)
+            t1.synchronize()
+            ms[name].append(t0.elapsed_time(t1) / args.reps)
+    px = args.width * args.height
+    record = dict(width=args.width, height=args.height, reps=args.reps, rounds=args.rounds, frames=args.frames,
+                  config="c3_chess", device=torch.cuda.get_device_name(0), hbm_peak_gbs=HBM_PEAK_GBS,
+                  build={w: (lib or renderers[0]._lib).rt_build_hash().decode() for w, lib in libs.items()},
+                  pixels_with_history_after_the_move=kept,
+                  traffic_floor_ms=dict(plain_stage=round(px * TEMPORAL_BYTES_PER_PIXEL / (HBM_PEAK_GBS * 1e9) * 1e3, 5),
+                                        motion_stage=round(px * MOTION_BYTES_PER_PIXEL / (HBM_PEAK_GBS * 1e9) * 1e3, 5)),
+                  series={k: dict(ms=round(float(np.median(v)), 5), ms_min=round(min(v), 5), ms_max=round(max(v), 5))
+                          for k, v in ms.items()})
+    if args.parent_lib:
+        for it in (0, 4):
+            par = [record["series"][f"plain_it{it}/{w}"] for w in ("parent", "parent_b")]
+            lo, hi = min(b["ms_min"] for b in par), max(b["ms_max"] for b in par)
+            record[f"plain_it{it}_parent_spread_ms"] = [lo, hi]
+            record[f"plain_it{it}_within_parent_spread"] = {
+                w: bool(lo <= record["series"][f"plain_it{it}/{w}"]["ms"] <= hi) for w in ("this", "this_b")}
+    for r in renderers:
+        r.close()
+    print(json.dumps(record), flush=True)
+    out = Path(args.out if args.out != "profiles/denoise/denoise_bench.json" else "profiles/temporal_motion/bench.json")
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(record, indent=1) + "\n")
 
 
 def main():
@@ -60,7 +164,11 @@ def main():
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--bench-line", default=None)
     ap.add_argument("--out", default="profiles/denoise/denoise_bench.json")
+    ap.add_argument("--motion", action="store_true")
+    ap.add_argument("--parent-lib", default=None)
     args = ap.parse_args()
+    if args.motion:
+        return motion_case(args)
     assert torch.cuda.is_available(), "denoise_bench needs a HIP device"
     dev = torch.device("cuda:0")
     frame_ms = None
