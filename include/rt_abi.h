@@ -58,7 +58,9 @@ extern "C" {
  * 12, additive: probe queries (rt_probe_sh, rt_probe_sh_device, rt_probe);
  * 12, additive: ambient queries (rt_ambient, rt_ambient_device, rt_ambient_point);
  * 12, additive: motion records for the temporal denoiser (rt_denoise_temporal_motion, rt_motion,
- * rt_motion_from_transforms, rt_read_feature_ids, rt_feature_ids_device). */
+ * rt_motion_from_transforms, rt_read_feature_ids, rt_feature_ids_device);
+ * 12, additive: lens queries (rt_lens, rt_lens_device, rt_lens_rays, rt_lens_rays_device,
+ * rt_lens_camera). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -789,6 +791,122 @@ RT_API int rt_ambient(rt_ctx* ctx, const rt_ambient_point* points, float* out /*
                       uint64_t count, uint32_t first_sample, uint32_t samples);
 RT_API int rt_ambient_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count,
                              uint32_t first_sample, uint32_t samples);
+
+/* ---- lens queries (ABI 12, additive: lens queries) ---------------------------
+ *
+ * "What does this camera see?" for cameras other than the context's pinhole: a thin lens (depth
+ * of field), an orthographic view, and an equirectangular panorama captured at a point (which
+ * rt_upload_env_map takes back as a reflection probe). The rays are drawn on the device from a
+ * 176-byte descriptor, a lens sample per (pixel, sample index), so no records cross the bus: a
+ * radiance query of the same rays needs one 32-byte rt_radiance_ray per pixel per sample. The
+ * image width x height belongs to the descriptor, not to the context's framebuffer; nothing of
+ * the framebuffer is read or written. */
+
+#define RT_LENS_PERSPECTIVE  0u
+#define RT_LENS_ORTHOGRAPHIC 1u
+#define RT_LENS_EQUIRECT     2u
+
+typedef struct rt_lens_camera {
+    float inverse_projection[16]; /* column-major, glam layout; PERSPECTIVE only */
+    float inverse_view[16];       /* column-major; used as a rotation only (w = 0); EQUIRECT ignores it */
+    float origin[3];
+    float aspect;                 /* the factor camera_ray multiplies nx by: f32(width)/f32(height) in a frame */
+    uint32_t kind;                /* RT_LENS_* */
+    uint32_t width, height;       /* the image the pixel indices refer to; width * height <= 2^32 */
+    uint32_t stream_base;         /* pixel i draws from the RNG stream stream_base + i */
+    float aperture;               /* lens radius in view units; 0 = pinhole; PERSPECTIVE only */
+    float focus;                  /* distance of the focal plane along the view axis, > 0 when aperture > 0 */
+    float ortho_half_height;      /* ORTHOGRAPHIC: half the view volume's height, > 0 */
+    float _pad;                   /* ignored */
+} rt_lens_camera;
+
+#if defined(__cplusplus)
+static_assert(sizeof(rt_lens_camera) == 176, "rt_lens_camera is 176 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rt_lens_camera) == 176, "rt_lens_camera is 176 bytes");
+#endif
+
+/* Items are the pixels first_pixel .. first_pixel + count - 1 of the descriptor's image in
+ * row-major order (pixel i = y*width + x); the caller tiles by ranges. rt_lens writes four floats
+ * per pixel of the range, in order; nothing outside [0, 4 * count) is written.
+ *
+ * THE LENS CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+ * written order, with no contraction. For pixel index i = y*width + x of the descriptor's image,
+ * stream = stream_base + i (u32, wrapping) and sample index u:
+ *  A. Screen point, as in camera_ray. xc = f32(x)/f32(width), yc = f32(y)/f32(height).
+ *     nx = xc*2.0f - 1.0f, ny = yc*2.0f - 1.0f, ax = nx*aspect.
+ *  B. PERSPECTIVE. t = P^-1 * (ax, ny, 1, 1) with glam's Mat4 * Vec4 =
+ *     ((c0*x + c1*y) + c2*z) + c3*w per component (P^-1 = inverse_projection, V^-1 = inverse_view).
+ *     ws = normalize(t.xyz / t.w) with normalize(v) = v * (1.0f / sqrt((x*x + y*y) + z*z)).
+ *     If aperture == 0: o = origin, d = (V^-1 * (ws, 0)).xyz: the very bits of camera_ray.
+ *     Otherwise: lseed = (stream * u * 326624u) ^ 0x85EBCA6Bu (u32, wrapping).
+ *     r1 = random(&lseed), r2 = random(&lseed), in that order (compute_shader.wgsl:587-599).
+ *     rad = aperture * sqrt(r1), th = 6.2831850051879883f * r2.
+ *     lx = rad * cos(th), ly = rad * cos(th - 1.5707963705062866f).
+ *     k = focus / (0.0f - ws.z), f = ws * k.
+ *     dv = normalize((f.x - lx, f.y - ly, f.z)), d = (V^-1 * (dv, 0)).xyz.
+ *     o = origin + (V^-1 * (lx, ly, 0, 0)).xyz.
+ *     cos is the oracle's oracle_cosf (cosf_c on the device; its arguments stay within
+ *     |x| <= 2 pi) and sqrt is correctly rounded.
+ *  C. ORTHOGRAPHIC. o = origin + (V^-1 * (ax*ortho_half_height, ny*ortho_half_height, 0, 0)).xyz.
+ *     d = (V^-1 * (0, 0, -1, 0)).xyz.
+ *  D. EQUIRECT. The inverse of environment_map_coords at pixel centres, world-aligned.
+ *     uc = (f32(x) + 0.5f)/f32(width), vc = (f32(y) + 0.5f)/f32(height).
+ *     az = (uc - 0.5f) * (2.0f*WGSL_PI), el = (vc - 0.5f) * WGSL_PI, ce = cos(el), with
+ *     WGSL_PI = 3.1415926536f.
+ *     d = (ce*cos(az), cos(el - 1.5707963705062866f), ce*cos(az - 1.5707963705062866f)). o = origin.
+ *  E. Path and sum. R = +0.0f on all four channels. For s = 0 .. samples-1 ascending,
+ *     u = first_sample + s (u32, wrapping); L_s is the result rt_radiance defines for the record
+ *     (o, stream, d) of step B, C or D at u with first_sample = u, samples = 1 and the call's
+ *     bounces, per_pixel's own jitter included. R = R + L_s per channel. radiance[i] = R.
+ * End of the lens contract.
+ *
+ * rt_lens_rays writes the rt_radiance_ray (o, stream, d, +0.0f) of steps A to D for
+ * u = sample_index, one per pixel of the range, in order.
+ *
+ * Consequences:
+ *  1. The pinhole case reproduces the frame: PERSPECTIVE with aperture == 0, stream_base == 0 and
+ *     the context's size, matrices (rt_update_camera_matrices), aspect and origin gives the
+ *     accumulation that `samples` frames from accumulation_index = first_sample leave in a zeroed
+ *     buffer, bit for bit.
+ *  2. rt_radiance on the records of rt_lens_rays(.., u) with first_sample = u, samples = 1 equals
+ *     rt_lens with first_sample = u, samples = 1.
+ *  3. bounces == 0 gives all-zero radiance and no segments, and is RT_OK. samples == 0 is
+ *     RT_E_INVALID (whatever `count` is). The caller divides by `samples`; nothing is clamped.
+ *  4. A pixel whose stream is 0 repeats its lens point (and its path) for every u, as pixel 0
+ *     repeats its seed in the reference: callers use stream_base >= 1 unless they want
+ *     consequence 1.
+ *  5. A draw of r1 == 0 gives the lens centre.
+ *  6. RT_E_INVALID for: an unknown kind; width or height 0; width * height > 2^32; a range
+ *     outside the image (first_pixel + count > width * height); aperture negative or not finite;
+ *     focus <= 0 (or NaN) with aperture > 0; ortho_half_height <= 0 (or NaN) for ORTHOGRAPHIC; a
+ *     NULL cam, radiance or rays pointer with count > 0; device pointers that are not device
+ *     memory of the context's device, or not aligned: 16 bytes for rays and radiance, 8 for
+ *     segments. count == 0 returns RT_OK and launches nothing.
+ *  7. Scene visibility, side effects (none a render can observe: queued frames stay queued),
+ *     independence of the brute-force mode and of every rt_set_tuning key, rank contexts, the
+ *     exactness domain and the counted segments are those of rt_radiance, for the rays of steps
+ *     B to D.
+ *
+ * `cam` is host memory in all four entry points and is read before the call returns.
+ * rt_lens, rt_lens_rays: host result pointers, synchronous; the range runs in chunks of tuning
+ * "query_chunk" pixels through the pinned buffer of rt_trace_rays (16 or 32 bytes out per pixel,
+ * nothing in). `segments` may be NULL.
+ * rt_lens_device, rt_lens_rays_device: device result pointers on the context's device;
+ * stream-ordered on rt_stream(ctx), no host copy, asynchronous; segments_device (may be NULL) is
+ * added to, not set.
+ * Tuning "query_lds_mode" selects the scene placement as for the ray queries; by default calls of
+ * fewer than 262144 walks (count * samples) read the scene from global memory. */
+RT_API int rt_lens(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count,
+                   float* radiance /* 4 floats per pixel */, uint32_t bounces, uint32_t first_sample,
+                   uint32_t samples, uint64_t* segments /* may be NULL */);
+RT_API int rt_lens_device(rt_ctx* ctx, const rt_lens_camera* cam /* host memory */, uint64_t first_pixel,
+                          uint64_t count, void* radiance_device, uint32_t bounces, uint32_t first_sample,
+                          uint32_t samples, void* segments_device /* may be NULL; one u64, added to */);
+RT_API int rt_lens_rays(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count,
+                        uint32_t sample_index, rt_radiance_ray* rays);
+RT_API int rt_lens_rays_device(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count,
+                               uint32_t sample_index, void* rays_device);
 
 /* ---- feature buffers and the denoiser (ABI 12, additive: denoiser) ----------
  *

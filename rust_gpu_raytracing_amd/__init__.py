@@ -5,7 +5,7 @@
 """
 from . import buffers, sh
 from ._native import NativeLibraryError, RtError, load_library
-from .camera import Camera
+from .camera import Camera, lens_camera
 from .renderer import REFERENCE_BOUNCES, Renderer
 from .scene import CONFIGS, RenderScene, build_config
 
@@ -19,6 +19,7 @@ __all__ = [
     "Renderer",
     "RtError",
     "build_config",
+    "lens_camera",
     "load_library",
     "sh",
 ]

@@ -107,6 +107,14 @@ class rt_probe(ctypes.Structure):
     _fields_ = [("position", ctypes.c_float * 3), ("stream", ctypes.c_uint32)]
 
 
+class rt_lens_camera(ctypes.Structure):
+    _fields_ = [("inverse_projection", ctypes.c_float * 16), ("inverse_view", ctypes.c_float * 16),
+                ("origin", ctypes.c_float * 3), ("aspect", ctypes.c_float), ("kind", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("stream_base", ctypes.c_uint32),
+                ("aperture", ctypes.c_float), ("focus", ctypes.c_float), ("ortho_half_height", ctypes.c_float),
+                ("_pad", ctypes.c_float)]
+
+
 class rt_hit(ctypes.Structure):
     _fields_ = [("t", ctypes.c_float), ("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
                 ("u", ctypes.c_float), ("v", ctypes.c_float), ("material_index", ctypes.c_uint32),
@@ -155,6 +163,8 @@ assert ctypes.sizeof(rt_radiance_ray) == 32
 assert ctypes.sizeof(rt_gather_point) == 32 and rt_gather_point.stream.offset == 12 and rt_gather_point.normal.offset == 16
 assert ctypes.sizeof(rt_ambient_point) == 32 and rt_ambient_point.stream.offset == 12 and rt_ambient_point.t_max.offset == 28
 assert ctypes.sizeof(rt_probe) == 16 and rt_probe.stream.offset == 12
+assert ctypes.sizeof(rt_lens_camera) == 176 and rt_lens_camera.origin.offset == 128 and rt_lens_camera.kind.offset == 144
+assert rt_lens_camera.aperture.offset == 160 and rt_lens_camera.ortho_half_height.offset == 168
 assert ctypes.sizeof(rt_ray_camera) == 16
 
 # name -> (restype, argtypes)
@@ -202,6 +212,11 @@ SIGNATURES = {
     "rt_probe_sh_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_ambient": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32]),
     "rt_ambient_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32]),
+    "rt_lens": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _U32, _U32, _U32,
+                               ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_lens_device": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _P, _U32, _U32, _U32, _P]),
+    "rt_lens_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _U32, _P]),
+    "rt_lens_rays_device": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint64, _U32, _P]),
     "rt_denoise_default_params":(ctypes.c_int, [ctypes.POINTER(rt_denoise_params)]),
     "rt_compute_features": (ctypes.c_int, [_P]),
     "rt_read_features": (ctypes.c_int, [_P, _P, _P]),
@@ -302,6 +317,7 @@ RT_DEFAULT_FRAME_BATCH = 16  # include/rt_abi.h (ABI 11)
 RT_PASS_PATH, RT_PASS_PRIMARY, RT_PASS_RESOLVE, RT_PASS_BRUTE, RT_PASS_BRUTE_STREAM = 1, 2, 4, 8, 16
 RT_PASS_PATH_FRAME_PAR = 64  # with RT_PASS_PATH: the path kernel's frame-parallel instance ran
 RT_GROUP_COPY_TRANSPORT = 1  # rt_create_multi_ex flags
+RT_LENS_PERSPECTIVE, RT_LENS_ORTHOGRAPHIC, RT_LENS_EQUIRECT = 0, 1, 2  # rt_lens_camera.kind
 RT_GATHER_IMAGE = 0
 RT_GATHER_ACCUMULATION = 1
 RT_DISPLAY_ACCUMULATION, RT_DISPLAY_DENOISED, RT_DISPLAY_PLANE = 0, 1, 2  # rt_display_params.source

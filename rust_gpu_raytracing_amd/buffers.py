@@ -126,6 +126,12 @@ AMBIENT_POINT = np.dtype([("position", "<f4", 3), ("stream", "<u4"), ("normal", 
 # rt_probe -- probe queries (rt_probe_sh): a point in free space and its RNG stream; the result is
 # nine float32 rgba coefficients per probe
 PROBE = np.dtype([("position", "<f4", 3), ("stream", "<u4")])
+# rt_lens_camera -- lens queries (rt_lens, rt_lens_rays): the descriptor the device draws a pixel's
+# rays from (camera.lens_camera builds it); the result is four float32 per pixel
+LENS_CAMERA = np.dtype([("inverse_projection", "<f4", 16), ("inverse_view", "<f4", 16), ("origin", "<f4", 3),
+                        ("aspect", "<f4"), ("kind", "<u4"), ("width", "<u4"), ("height", "<u4"), ("stream_base", "<u4"),
+                        ("aperture", "<f4"), ("focus", "<f4"), ("ortho_half_height", "<f4"), ("_pad", "<f4")])
+LENS_PERSPECTIVE, LENS_ORTHOGRAPHIC, LENS_EQUIRECT = 0, 1, 2  # rt_lens_camera.kind
 # rt_denoise_params -- the guided a-trous filter (rt_denoise); defaults {4, 1.0, 0.1, 0.05}
 DENOISE_PARAMS = np.dtype([("iterations", "<u4"), ("sigma_color", "<f4"), ("sigma_albedo", "<f4"),
                            ("sigma_depth", "<f4")])
@@ -141,7 +147,7 @@ DISPLAY_PARAMS = np.dtype([("source", "<u4"), ("tone_operator", "<u4"), ("encode
 for _dt, _size in (
     (PARAMS, 48), (RAY_CAMERA, 16), (RAY, 16), (SPHERE, 32), (TRIANGLE, 112),
     (MATERIAL, 32), (OBJECT_INFO, 48), (SUB_OBJECT_INFO, 32), (OBJECT_TRANSFORM, 32),
-    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (AMBIENT_POINT, 32), (PROBE, 16), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
+    (QUERY_RAY, 32), (HIT, 64), (OCCLUSION_RAY, 32), (RADIANCE_RAY, 32), (GATHER_POINT, 32), (AMBIENT_POINT, 32), (PROBE, 16), (LENS_CAMERA, 176), (DENOISE_PARAMS, 16), (TEMPORAL_PARAMS, 80),
     (DISPLAY_PARAMS, 48),
 ):
     assert _dt.itemsize == _size, (_dt, _size)

@@ -143,3 +143,31 @@ class Camera:
         rays = np.zeros(w * h, B.RAY)
         rays["direction"] = d
         return rays
+
+
+LENS_KINDS = {"perspective": B.LENS_PERSPECTIVE, "orthographic": B.LENS_ORTHOGRAPHIC, "equirect": B.LENS_EQUIRECT}
+
+
+def lens_camera(camera: Camera, kind="perspective", aperture: float = 0.0, focus: float = 1.0,
+                ortho_half_height: float = 1.0, width: int | None = None, height: int | None = None,
+                stream_base: int = 0) -> np.ndarray:
+    """One ``buffers.LENS_CAMERA`` record (rt_lens_camera, include/rt_abi.h) from a ``Camera``: its
+    inverse matrices and position, the aspect factor ``recalculate_ray_directions`` multiplies by
+    (f32(width) / f32(height)), and the image size ``width`` x ``height`` (default: the camera's
+    viewport). ``kind``: "perspective" (``aperture`` > 0: a thin lens of that radius focused at the
+    distance ``focus`` along the view axis; 0: the pinhole), "orthographic" (a view volume of height
+    2 x ``ortho_half_height``) or "equirect" (a world-aligned panorama at the camera's position), or
+    the RT_LENS_* number. Pixel i draws from the RNG stream ``stream_base`` + i: with the defaults the
+    record reproduces the camera's frame (stream_base 0); use 1 or more with a lens, because stream
+    0 repeats its lens point."""
+    w = camera.viewport_width if width is None else int(width)
+    h = camera.viewport_height if height is None else int(height)
+    cam = np.zeros((), B.LENS_CAMERA)
+    cam["inverse_projection"] = np.asarray(camera.inverse_projection, np.float32).reshape(16)
+    cam["inverse_view"] = np.asarray(camera.inverse_view, np.float32).reshape(16)
+    cam["origin"] = camera.position
+    cam["aspect"] = f32(w) / f32(h) if h else f32(0.0)
+    cam["kind"] = LENS_KINDS[kind] if isinstance(kind, str) else int(kind)
+    cam["width"], cam["height"], cam["stream_base"] = w, h, stream_base
+    cam["aperture"], cam["focus"], cam["ortho_half_height"] = aperture, focus, ortho_half_height
+    return cam

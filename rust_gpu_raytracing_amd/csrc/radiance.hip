@@ -94,8 +94,55 @@
 //    again from (stream, u) with the path kernel's own function -- the scratch holds no
 //    directions: 16 B per path, not 32 -- and adds the 36 products in sample order; then six
 //    shuffle levels on each of the 36 values and nine 16-B stores.
+//
+// Lens queries (rt_lens, rt_lens_device, rt_lens_rays, rt_lens_rays_device) run on
+// the same kernel body, instantiated with kPathLens, and on rt_lens_rays_kernel below. The contract,
+// as in include/rt_abi.h:
+//
+// THE LENS CONTRACT. Everything is f32. Each written operation is one IEEE operation, in the
+// written order, with no contraction. For pixel index i = y*width + x of the descriptor's image,
+// stream = stream_base + i (u32, wrapping) and sample index u:
+//  A. Screen point, as in camera_ray. xc = f32(x)/f32(width), yc = f32(y)/f32(height).
+//     nx = xc*2.0f - 1.0f, ny = yc*2.0f - 1.0f, ax = nx*aspect.
+//  B. PERSPECTIVE. t = P^-1 * (ax, ny, 1, 1) with glam's Mat4 * Vec4 =
+//     ((c0*x + c1*y) + c2*z) + c3*w per component (P^-1 = inverse_projection, V^-1 = inverse_view).
+//     ws = normalize(t.xyz / t.w) with normalize(v) = v * (1.0f / sqrt((x*x + y*y) + z*z)).
+//     If aperture == 0: o = origin, d = (V^-1 * (ws, 0)).xyz: the very bits of camera_ray.
+//     Otherwise: lseed = (stream * u * 326624u) ^ 0x85EBCA6Bu (u32, wrapping).
+//     r1 = random(&lseed), r2 = random(&lseed), in that order (compute_shader.wgsl:587-599).
+//     rad = aperture * sqrt(r1), th = 6.2831850051879883f * r2.
+//     lx = rad * cos(th), ly = rad * cos(th - 1.5707963705062866f).
+//     k = focus / (0.0f - ws.z), f = ws * k.
+//     dv = normalize((f.x - lx, f.y - ly, f.z)), d = (V^-1 * (dv, 0)).xyz.
+//     o = origin + (V^-1 * (lx, ly, 0, 0)).xyz.
+//     cos is the oracle's oracle_cosf (cosf_c on the device; its arguments stay within
+//     |x| <= 2 pi) and sqrt is correctly rounded.
+//  C. ORTHOGRAPHIC. o = origin + (V^-1 * (ax*ortho_half_height, ny*ortho_half_height, 0, 0)).xyz.
+//     d = (V^-1 * (0, 0, -1, 0)).xyz.
+//  D. EQUIRECT. The inverse of environment_map_coords at pixel centres, world-aligned.
+//     uc = (f32(x) + 0.5f)/f32(width), vc = (f32(y) + 0.5f)/f32(height).
+//     az = (uc - 0.5f) * (2.0f*WGSL_PI), el = (vc - 0.5f) * WGSL_PI, ce = cos(el), with
+//     WGSL_PI = 3.1415926536f.
+//     d = (ce*cos(az), cos(el - 1.5707963705062866f), ce*cos(az - 1.5707963705062866f)). o = origin.
+//  E. Path and sum. R = +0.0f on all four channels. For s = 0 .. samples-1 ascending,
+//     u = first_sample + s (u32, wrapping); L_s is the result rt_radiance defines for the record
+//     (o, stream, d) of step B, C or D at u with first_sample = u, samples = 1 and the call's
+//     bounces, per_pixel's own jitter included. R = R + L_s per channel. radiance[i] = R.
+// End of the lens contract.
+//
+//  * The work item is a pixel of the call's range, and the control flow is a radiance query's: the
+//    samples of a pixel run back to back on its lane and are summed in order. One place differs:
+//    the sample start, which draws the ray (lens_ray of rt_query_frame.h, steps A to D) instead of
+//    loading a record, then start_sample_at.
+//  * The descriptor is not a kernel argument (RadianceArgs and the other kinds' code stay as they
+//    are): qa.rays points to a copy of it in device memory the context owns, read at wave-uniform
+//    addresses, and qa.stripes carries the launch's first pixel. The copy is written on the launch's
+//    stream by rt_lens_store_kernel, which takes the descriptor by value: stream order keeps a
+//    launch in flight from seeing the next call's descriptor.
+//  * rt_lens_rays_kernel writes the records of steps A to D, one thread per pixel, two 16-B stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "rt_launch.h"
 #include "rt_path_common.h"
@@ -120,10 +167,11 @@ struct RadianceArgs {
     uint32_t first_sample;                      // random_index of a ray's first sample (:154)
     uint32_t samples;                           // samples per ray, >= 1 (ka.bounces >= 1 too: the host answers 0)
     uint32_t stripes;                           // kPathGather: stripes per point, min(samples, 64)
+                                                // kPathLens: the launch's first pixel (below 2^32)
 };
 
 // What the body of rt_radiance_kernel answers.
-enum PathKind : int { kPathRadiance = 0, kPathGather = 1, kPathProbe = 2 };
+enum PathKind : int { kPathRadiance = 0, kPathGather = 1, kPathProbe = 2, kPathLens = 3 };
 
 // Step 2 of the probe contract: the direction of the sample with index u of a probe's stream. The
 // path kernel and the resolve kernel both call this, so both hold the same bits.
@@ -141,11 +189,14 @@ __device__ __forceinline__ f3 probe_direction(uint32_t stream, uint32_t u) {
 // kPathProbe: the path kernel of a probe query (the probe contract above). A "ray" is a (probe,
 // sample) item: qa.rays holds rt_probe records, 16 B each, qa.count the launch's items (probes x
 // qa.samples, below 2^32), and qa.radiance the scratch, one float4 per item.
+// kPathLens: the path kernel of a lens query (the lens contract above). A "ray" is a pixel of the
+// launch's range: qa.rays points to the context's copy of the rt_lens_camera, qa.stripes is the
+// range's first pixel, qa.count its pixels and qa.radiance one float4 per pixel of the range.
 template <int kMode, bool kTris, uint32_t kThreads, PathKind kKind = kPathRadiance>
 __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka, RadianceArgs qa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr bool kAux = kMode >= 1;
-    constexpr bool kGather = kKind == kPathGather, kProbe = kKind == kPathProbe;
+    constexpr bool kGather = kKind == kPathGather, kProbe = kKind == kPathProbe, kLens = kKind == kPathLens;
     // The path kernel's LDS image without the camera block: what the walk, the record and shading
     // read.
     SceneView sv = global_scene_view<kMode, kTris>(ka, ka.srgb);
@@ -175,8 +226,15 @@ __global__ void __launch_bounds__(kThreads, 1) rt_radiance_kernel(KernelArgs ka,
     // kGather: `ray` is point * 64 + stripe (the item's slot among the partials) and `sample` the
     // sample index s; the origin and the direction are steps 1 and 2 of the contract.
     // kProbe: `ray` is the item t; one 16-B load reads the probe's record.
+    // kLens: `ray` is the pixel's position in the range; the ray is drawn from the descriptor.
     auto begin_sample = [&]() {
-        if constexpr (kProbe) {
+        if constexpr (kLens) {
+            const rt_lens_camera* __restrict__ cam = reinterpret_cast<const rt_lens_camera*>(qa.rays);
+            const uint32_t pixel = qa.stripes + (uint32_t)ray;
+            const uint32_t stream = cam->stream_base + pixel, u = qa.first_sample + sample;
+            const LensRay r = lens_ray(cam, pixel, stream, u);
+            start_sample_at(r.o, stream, u, r.d, p);
+        } else if constexpr (kProbe) {
             const uint32_t probe = (uint32_t)ray / qa.samples, s = (uint32_t)ray - probe * qa.samples;
             const float4 r0 = qa.rays[probe];
             const uint32_t stream = __float_as_uint(r0.w), u = qa.first_sample + s;
@@ -354,7 +412,33 @@ __global__ void __launch_bounds__(kResolveThreads) rt_probe_resolve_kernel(const
     }
 }
 
-// The instances, (mode, triangles, threads), each for the three kinds: f(kernel, threads) for the
+// The context's copy of a call's descriptor: the descriptor arrives by value, as a kernel argument,
+// so the write is ordered on the stream like the launches that read the copy, and nothing of the
+// caller's memory is read after the call. One lane, eleven 16-B stores at constant offsets.
+struct LensWords {
+    uint4 q[sizeof(rt_lens_camera) / 16u];
+};
+static_assert(sizeof(LensWords) == sizeof(rt_lens_camera), "rt_lens_camera is a whole number of 16-B words");
+__global__ void __launch_bounds__(64) rt_lens_store_kernel(LensWords cam, uint4* __restrict__ slot) {
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (uint32_t k = 0; k < sizeof(LensWords) / 16u; ++k) slot[k] = cam.q[k];
+}
+
+// rt_lens_rays: the records (o, stream, d, +0.0f) of steps A to D of the lens contract for the
+// pixels first_pixel .. first_pixel + count - 1 and the sample index u, one thread per pixel.
+__global__ void __launch_bounds__(kResolveThreads) rt_lens_rays_kernel(const rt_lens_camera* __restrict__ cam,
+                                                                      float4* __restrict__ rays, uint32_t first_pixel,
+                                                                      unsigned long long count, uint32_t u) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * kResolveThreads + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t pixel = first_pixel + (uint32_t)i, stream = cam->stream_base + pixel;
+    const LensRay r = lens_ray(cam, pixel, stream, u);
+    rays[2ull * i] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(stream));
+    rays[2ull * i + 1ull] = make_float4(r.d.x, r.d.y, r.d.z, 0.0f);
+}
+
+// The instances, (mode, triangles, threads), each for the four kinds: f(kernel, threads) for the
 // one of (mode, tris, kind). Workgroup size by placement: the global-memory instance has
 // no image to share: small workgroups, as the closest-hit query's. The staged instances share one
 // image among as many waves as their registers allow without spilling: the walks from global
@@ -389,6 +473,11 @@ hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* block
 
 hipError_t rt_probe_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
     return with_radiance_instance<kPathProbe>(
+        mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
+}
+
+hipError_t rt_lens_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return with_radiance_instance<kPathLens>(
         mode, tris, [&](auto kernel, uint32_t t) { return query_occupancy_of(kernel, t, lds_bytes, blocks_per_cu); });
 }
 
@@ -429,6 +518,36 @@ hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size
                                  hipStream_t stream) {
     return launch_path_kind<kPathProbe>(ka, mode, tris, lds_bytes, s, probes, lights, count, counter, segments,
                                         first_sample, samples, 0u, stream);
+}
+
+// Writes the context's copy `slot` (device memory, 16-byte aligned) of a lens descriptor,
+// stream-ordered: after every launch that reads the previous copy, before those that follow.
+hipError_t rt_launch_lens_camera(const rt_lens_camera& cam, void* slot, hipStream_t stream) {
+    LensWords w;
+    memcpy(&w, &cam, sizeof(w));
+    hipLaunchKernelGGL(rt_lens_store_kernel, dim3(1), dim3(64), 0, stream, w, static_cast<uint4*>(slot));
+    return hipGetLastError();
+}
+
+// The path kernel of a lens query: the `count` pixels from `first_pixel` on of the image of the
+// descriptor at `cam` (the context's copy, device memory) into `radiance`, one float4 per pixel.
+hipError_t rt_launch_lens(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                          const void* cam, void* radiance, uint32_t first_pixel, uint64_t count,
+                          unsigned long long* counter, unsigned long long* segments, uint32_t first_sample,
+                          uint32_t samples, hipStream_t stream) {
+    return launch_path_kind<kPathLens>(ka, mode, tris, lds_bytes, s, cam, radiance, count, counter, segments,
+                                       first_sample, samples, first_pixel, stream);
+}
+
+// The records of the same pixels for the sample index u into `rays`, 32 bytes per pixel.
+hipError_t rt_launch_lens_rays(const void* cam, void* rays, uint32_t first_pixel, uint64_t count, uint32_t u,
+                               hipStream_t stream) {
+    if (count == 0) return hipSuccess;
+    const uint64_t blocks = (count + kResolveThreads - 1u) / kResolveThreads;  // count <= 2^32: at most 2^24
+    hipLaunchKernelGGL(rt_lens_rays_kernel, dim3((uint32_t)blocks), dim3(kResolveThreads), 0, stream,
+                       static_cast<const rt_lens_camera*>(cam), static_cast<float4*>(rays), first_pixel,
+                       (unsigned long long)count, u);
+    return hipGetLastError();
 }
 
 // Step 4's tree over the partials of `points` points (stream-ordered after the path kernel).

@@ -395,6 +395,7 @@ struct rt_ctx {
     void* d_probe_lights = nullptr;                 // rt_probe_sh: one float4 per path of a launch
     size_t probe_lights_bytes = 0;
     unsigned long long* d_probe_next = nullptr;     // the chunk counters of the two launches in flight
+    uint4* d_lens_cam = nullptr;                    // rt_lens: the descriptor the launches of a call read
     int q_occ_mode = -1;                        // occupancy of the last query instance
     int q_occ_kind = 0;                         // (which kernel's: QueryKind)
     bool q_occ_tris = false;
@@ -936,7 +937,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_lens_cam, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out, ctx->d_disp_out, ctx->d_disp_meter,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
                     ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2],
@@ -1877,26 +1878,29 @@ static int query_enter(rt_ctx* ctx) {
 // `kind`: the kernel the view is for -- rt_query_kernel, rt_occlusion_kernel (occlusion.hip) or
 // rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
 // its gather instance (points x samples) or its probe instance (probes x samples), or
-// rt_ambient_kernel (ambient.hip; points x samples).
+// rt_ambient_kernel (ambient.hip; points x samples), or the radiance kernel's lens instance
+// (pixels x samples).
 enum QueryKind {
     kQueryClosest = 0,
     kQueryAnyHit = 1,
     kQueryRadiance = 2,
     kQueryGather = 3,
     kQueryProbe = 4,
-    kQueryAmbient = 5
+    kQueryAmbient = 5,
+    kQueryLens = 6
 };
 
 // Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
 static const struct {
     uint32_t (*threads)(int mode, bool tris);
     hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-} kQueryKernels[6] = {{rt_query_threads, rt_query_occupancy},
+} kQueryKernels[7] = {{rt_query_threads, rt_query_occupancy},
                       {rt_occlusion_threads, rt_occlusion_occupancy},
                       {rt_radiance_threads, rt_radiance_occupancy},
                       {rt_radiance_threads, rt_gather_occupancy},
                       {rt_radiance_threads, rt_probe_occupancy},
-                      {rt_ambient_threads, rt_ambient_occupancy}};
+                      {rt_ambient_threads, rt_ambient_occupancy},
+                      {rt_radiance_threads, rt_lens_occupancy}};
 
 struct QueryLaunch {
     KernelArgs ka{};
@@ -2828,6 +2832,162 @@ int rt_probe_sh(rt_ctx* ctx, const rt_probe* probes, float* sh, uint64_t count, 
                 uint32_t samples, uint64_t* segments) {
     return staged_query(ctx, kProbeSh, probes, sh, count, samples, segments,
                         bind_path_run(run_probe_sh, ctx, bounces, first_sample, samples));
+}
+
+// ---- lens queries (radiance.hip, kPathLens) -----------------------------------------------------
+//
+// Per pixel of a range of the descriptor's image, the summed light of `samples` paths whose first
+// ray is drawn on the device from the descriptor (the contract in include/rt_abi.h). The path
+// kernel is the radiance kernel's lens instance over the range's pixels; rt_lens_rays_kernel writes
+// the same rays as records. The launches read the descriptor from the context's copy
+// (d_lens_cam), which rt_lens_store_kernel writes on the primary stream from a kernel argument:
+// every lens launch runs on that stream too, so the copy changes only after the launches that read
+// the earlier one and before those that follow, whatever the host does in between. (The chunks of
+// a host form share the copy of their call; the auxiliary stream runs no lens launch.)
+
+constexpr QueryFamily kLens = {"rt_lens", "rt_lens_device", "cam", "radiance", 0, 16, 16, kAnySamples, true};
+constexpr QueryFamily kLensRays = {"rt_lens_rays", "rt_lens_rays_device", "cam", "rays", 0, 32, 16, 0, false};
+
+// Consequence 6 of the lens contract, for the range [first_pixel, first_pixel + count), count > 0.
+static int check_lens(rt_ctx* ctx, const char* entry, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count) {
+    auto bad = [&](const char* why) { return fail(ctx, RT_E_INVALID, std::string(entry) + ": " + why); };
+    if (!cam) return bad("cam is NULL");
+    if (cam->kind > RT_LENS_EQUIRECT) return bad("unknown kind");
+    if (cam->width == 0 || cam->height == 0) return bad("width or height is 0");
+    const uint64_t pixels = (uint64_t)cam->width * cam->height;  // (below 2^64)
+    if (pixels > (1ull << 32)) return bad("width * height above 2^32");
+    if (first_pixel > pixels || count > pixels - first_pixel) return bad("the range lies outside the image");
+    if (!(cam->aperture >= 0.0f) || std::isinf(cam->aperture)) return bad("aperture is negative or not finite");
+    if (cam->kind == RT_LENS_PERSPECTIVE && cam->aperture > 0.0f && !(cam->focus > 0.0f))
+        return bad("focus must be > 0 when aperture > 0");
+    if (cam->kind == RT_LENS_ORTHOGRAPHIC && !(cam->ortho_half_height > 0.0f)) return bad("ortho_half_height must be > 0");
+    return RT_OK;
+}
+
+// The context's copy of `cam` for the launches that follow on the primary stream.
+static int stage_lens_camera(rt_ctx* ctx, const rt_lens_camera* cam) {
+    if (!ctx->d_lens_cam) {
+        const int rc = dev_alloc(ctx, &ctx->d_lens_cam, sizeof(rt_lens_camera) / sizeof(uint4));
+        if (rc) return rc;
+    }
+    const hipError_t e = rt_launch_lens_camera(*cam, ctx->d_lens_cam, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_lens_store_kernel launch", e);
+    return RT_OK;
+}
+
+// Path-traces the `count` pixels from `first_pixel` on of the staged descriptor's image into
+// `radiance`, stream-ordered on the primary stream; the counted segments are added to the device
+// counter `segments` (null: not counted).
+static int run_lens(rt_ctx* ctx, uint64_t first_pixel, void* radiance, uint64_t count, uint32_t bounces,
+                    uint32_t first_sample, uint32_t samples, unsigned long long* segments) {
+    if (count == 0) return RT_OK;
+    if (bounces == 0) return answer_zero_bounces(ctx, radiance, count, 16u);
+    QueryLaunch q;
+    const int rc = path_query_scene(ctx, count, bounces, samples, kQueryLens, q);
+    if (rc) return rc;
+    const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident, rtq::kRadianceFirstChunkMax,
+                                                     rtq::kRadianceChunkMax);
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    // (first_pixel < width * height <= 2^32 with count > 0: check_lens)
+    const hipError_t e = rt_launch_lens(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, ctx->d_lens_cam, radiance,
+                                        (uint32_t)first_pixel, count, ctx->d_query_next, segments, first_sample,
+                                        samples, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_radiance_kernel (lens) launch", e);
+    return RT_OK;
+}
+
+// The host form of a lens entry point, which has no input records: the range runs in chunks of
+// "query_chunk" pixels, run(first pixel, device out, n, device segment counter or null) answers a
+// chunk into the device scratch where the results of a closest-hit chunk go, and `out_bytes` per
+// pixel come back to `out` through the pinned buffer. The segment counter as in staged_query.
+extern "C++" template <class Run>
+static int staged_pixels(rt_ctx* ctx, const QueryFamily& f, uint64_t first_pixel, void* out, uint64_t count,
+                         uint64_t* segments, Run run) {
+    int rc;
+    if (f.segments && !ctx->d_radiance_segs && (rc = dev_alloc(ctx, &ctx->d_radiance_segs, 1))) return rc;
+    const size_t out_bytes = f.out_bytes;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, ctx->query_chunk);
+    if ((rc = query_buffers(ctx, chunk))) return rc;
+    unsigned char* d_out = static_cast<unsigned char*>(ctx->d_query_buf) + ctx->query_buf_rays * sizeof(rt_query_ray);
+    unsigned char* h_out = static_cast<unsigned char*>(ctx->query_pinned) + ctx->query_pinned_rays * sizeof(rt_query_ray);
+    unsigned long long* h_segs = reinterpret_cast<unsigned long long*>(h_out + chunk * out_bytes);
+    unsigned long long* d_segs = f.segments ? ctx->d_radiance_segs : nullptr;
+    if (d_segs) RT_HIP(ctx, hipMemsetAsync(d_segs, 0, sizeof(unsigned long long), ctx->stream));
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        if ((rc = run(first_pixel + done, d_out, n, d_segs))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_out, d_out, n * out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (d_segs && done + n == count)
+            RT_HIP(ctx, hipMemcpyAsync(h_segs, d_segs, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(static_cast<unsigned char*>(out) + done * out_bytes, h_out, n * out_bytes);
+        done += n;
+    }
+    if (d_segs && segments) *segments = *h_segs;
+    return RT_OK;
+}
+
+int rt_lens_device(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count, void* radiance_device,
+                   uint32_t bounces, uint32_t first_sample, uint32_t samples, void* segments_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_samples(ctx, kLens, kLens.device, samples);
+    if (rc || count == 0) return rc;
+    if ((rc = check_lens(ctx, kLens.device, cam, first_pixel, count))) return rc;
+    rc = check_device_ptrs(ctx, kLens.device, {{radiance_device, kLens.out, 16, false}, {segments_device, "segments", 8, true}});
+    if (rc || (rc = query_enter(ctx)) || (rc = stage_lens_camera(ctx, cam))) return rc;
+    return run_lens(ctx, first_pixel, radiance_device, count, bounces, first_sample, samples,
+                    static_cast<unsigned long long*>(segments_device));
+}
+
+int rt_lens(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count, float* radiance,
+            uint32_t bounces, uint32_t first_sample, uint32_t samples, uint64_t* segments) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_samples(ctx, kLens, kLens.host, samples);
+    if (rc) return rc;
+    if (count == 0) {
+        if (segments) *segments = 0;
+        return RT_OK;
+    }
+    if ((rc = check_lens(ctx, kLens.host, cam, first_pixel, count))) return rc;
+    if (!radiance) return fail(ctx, RT_E_INVALID, "rt_lens: radiance is NULL");
+    if ((rc = query_enter(ctx)) || (rc = stage_lens_camera(ctx, cam))) return rc;
+    return staged_pixels(ctx, kLens, first_pixel, radiance, count, segments,
+                         [=](uint64_t first, void* out, uint64_t n, unsigned long long* segs) {
+                             return run_lens(ctx, first, out, n, bounces, first_sample, samples, segs);
+                         });
+}
+
+// The records of the range's rays (steps A to D for the sample index u): no scene, nothing but the
+// descriptor is read.
+static int run_lens_rays(rt_ctx* ctx, uint64_t first_pixel, void* rays, uint64_t count, uint32_t u) {
+    const hipError_t e = rt_launch_lens_rays(ctx->d_lens_cam, rays, (uint32_t)first_pixel, count, u, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_lens_rays_kernel launch", e);
+    return RT_OK;
+}
+
+int rt_lens_rays_device(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count,
+                        uint32_t sample_index, void* rays_device) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    int rc = check_lens(ctx, kLensRays.device, cam, first_pixel, count);
+    if (rc) return rc;
+    rc = check_device_ptrs(ctx, kLensRays.device, {{rays_device, kLensRays.out, 16, false}});
+    if (rc || (rc = stage_lens_camera(ctx, cam))) return rc;
+    return run_lens_rays(ctx, first_pixel, rays_device, count, sample_index);
+}
+
+int rt_lens_rays(rt_ctx* ctx, const rt_lens_camera* cam, uint64_t first_pixel, uint64_t count, uint32_t sample_index,
+                 rt_radiance_ray* rays) {
+    RT_ENTER_NOFLUSH(ctx);
+    if (count == 0) return RT_OK;
+    int rc = check_lens(ctx, kLensRays.host, cam, first_pixel, count);
+    if (rc) return rc;
+    if (!rays) return fail(ctx, RT_E_INVALID, "rt_lens_rays: rays is NULL");
+    if ((rc = stage_lens_camera(ctx, cam))) return rc;
+    return staged_pixels(ctx, kLensRays, first_pixel, rays, count, nullptr,
+                         [=](uint64_t first, void* out, uint64_t n, unsigned long long*) {
+                             return run_lens_rays(ctx, first, out, n, sample_index);
+                         });
 }
 
 int rt_read_output(rt_ctx* ctx, uint32_t* out) {

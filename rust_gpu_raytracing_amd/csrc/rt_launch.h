@@ -91,6 +91,14 @@ hipError_t rt_launch_probe_paths(const KernelArgs& ka, int mode, bool tris, size
                                  hipStream_t stream);
 hipError_t rt_launch_probe_resolve(const void* lights, const void* probes, void* sh, uint32_t count, uint32_t first_sample,
                                    uint32_t samples, hipStream_t stream);
+hipError_t rt_lens_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_lens_camera(const rt_lens_camera& cam, void* slot, hipStream_t stream);
+hipError_t rt_launch_lens(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                          const void* cam, void* radiance, uint32_t first_pixel, uint64_t count,
+                          unsigned long long* counter, unsigned long long* segments, uint32_t first_sample,
+                          uint32_t samples, hipStream_t stream);
+hipError_t rt_launch_lens_rays(const void* cam, void* rays, uint32_t first_pixel, uint64_t count, uint32_t u,
+                               hipStream_t stream);
 uint32_t rt_ambient_threads(int mode, bool tris);
 hipError_t rt_ambient_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
 hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_abi.h"
 #include "rt_path_common.h"
 #include "rt_query_schedule.h"
 #include "rt_walk.h"
@@ -224,6 +225,67 @@ __device__ __forceinline__ f3 gather_direction(f3 n, uint32_t stream, uint32_t u
     const float gy = normal01(dseed);
     const float gz = normal01(dseed);
     return normalize(n + mk(gx, gy, gz));
+}
+
+// Steps A to D of the lens contract (include/rt_abi.h; radiance.hip repeats it): the ray (o, d) of
+// pixel `pixel` of the descriptor's image for the sample index u of its stream. The lens instance
+// of rt_radiance_kernel and rt_lens_rays_kernel both call this, so both hold the same bits. `cam`
+// is device memory read at wave-uniform addresses; the host has checked kind, width and height.
+// (The ray comes back by value from one exit: with two out-pointers and a return per kind the
+// callers' o and d went through scratch memory.)
+struct LensRay {
+    f3 o, d;
+};
+
+__device__ __forceinline__ LensRay lens_ray(const rt_lens_camera* __restrict__ cam, uint32_t pixel, uint32_t stream,
+                                            uint32_t u) {
+    const uint32_t y = pixel / cam->width, x = pixel - y * cam->width;
+    const f3 origin = mk(cam->origin[0], cam->origin[1], cam->origin[2]);
+    if (cam->kind == RT_LENS_EQUIRECT) {
+        const float uc = ((float)x + 0.5f) / (float)cam->width;
+        const float vc = ((float)y + 0.5f) / (float)cam->height;
+        const float az = (uc - 0.5f) * kTwoPiWgsl;
+        const float el = (vc - 0.5f) * kWgslPi;
+        const float ce = cosf_c(el);
+        return LensRay{origin,
+                       mk(ce * cosf_c(az), cosf_c(el - 1.5707963705062866f), ce * cosf_c(az - 1.5707963705062866f))};
+    }
+    const float xc = (float)x / (float)cam->width;
+    const float yc = (float)y / (float)cam->height;
+    const float nx = xc * 2.0f - 1.0f;
+    const float ny = yc * 2.0f - 1.0f;
+    const float ax = nx * cam->aspect;
+    // in view space: the direction v and, for the kinds that leave the origin, the offset (px, py, 0)
+    f3 v = mk(0.0f, 0.0f, -1.0f);
+    float px = 0.0f, py = 0.0f;
+    bool shifted = true;
+    if (cam->kind == RT_LENS_ORTHOGRAPHIC) {
+        px = ax * cam->ortho_half_height;
+        py = ny * cam->ortho_half_height;
+    } else {
+        float tw;
+        const f3 t = mat4_mul_xyz(cam->inverse_projection, ax, ny, 1.0f, 1.0f, tw);
+        const f3 ws = normalize(mk(t.x / tw, t.y / tw, t.z / tw));
+        if (cam->aperture == 0.0f) {  // camera_ray (rt_path_common.h), operation for operation
+            v = ws;
+            shifted = false;
+        } else {
+            uint32_t lseed = (stream * u * 326624u) ^ 0x85EBCA6Bu;
+            const float r1 = random01(lseed);
+            const float r2 = random01(lseed);
+            const float rad = cam->aperture * sqrt_rn_any(r1);
+            const float th = kBoxMullerTwoPi * r2;
+            px = rad * cosf_c(th);
+            py = rad * cosf_c(th - 1.5707963705062866f);
+            const float k = cam->focus / (0.0f - ws.z);
+            const f3 f = ws * k;
+            v = normalize(mk(f.x - px, f.y - py, f.z));
+        }
+    }
+    float unused;
+    const f3 d = mat4_mul_xyz(cam->inverse_view, v.x, v.y, v.z, 0.0f, unused);
+    const f3 off = mat4_mul_xyz(cam->inverse_view, px, py, 0.0f, 0.0f, unused);
+    return LensRay{shifted ? origin + off : origin, d};
 }
 
 // ---- the traversal step --------------------------------------------------------------------------

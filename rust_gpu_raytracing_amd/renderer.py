@@ -547,6 +547,73 @@ class Renderer:
                    int(samples), ctypes.byref(segments))
         return (out, segments.value) if return_segments else out
 
+    # ------------------------------------------------------------------ lens queries
+    @staticmethod
+    def _lens_range(cam, region):
+        """(the descriptor as one C-contiguous LENS_CAMERA record, first pixel, count, result shape)
+        for ``region``: None (the whole image) or (first_pixel, count)."""
+        cam = np.ascontiguousarray(np.asarray(cam, B.LENS_CAMERA).reshape(1))
+        w, h = int(cam["width"][0]), int(cam["height"][0])
+        if region is None:
+            return cam, 0, w * h, (h, w)
+        first, count = (int(v) for v in region)
+        return cam, first, count, (count,)
+
+    def lens(self, cam, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1, samples: int = 1, region=None,
+             device: bool = False, return_segments: bool = False):
+        """What a thin-lens, orthographic or equirectangular camera sees (rt_lens): per pixel of the
+        descriptor's image, the sum over ``samples`` paths whose first ray is drawn on the device
+        from ``cam`` (a ``buffers.LENS_CAMERA`` record; ``camera.lens_camera`` builds one) by the lens
+        contract of include/rt_abi.h. Divide by ``samples`` for the mean; nothing is clamped. Against
+        the scene as it is now, without touching the framebuffer or anything else a render reads.
+
+        Returns an (h, w, 4) float32 array, or with ``region`` = (first_pixel, count) -- a row-major
+        range of pixels, which is how callers tile -- a (count, 4) array; with ``return_segments``
+        also the call's counted ray segments. With ``device`` the result stays on the GPU
+        (rt_lens_device, stream-ordered on the context's stream) and comes back as a CUDA tensor."""
+        cam, first, count, shape = self._lens_range(cam, region)
+        scalars = (int(bounces), int(first_sample), int(samples))
+        if device:
+            return self._lens_device("rt_lens_device", cam, first, count, shape + (4,), scalars, bool(return_segments))
+        out = np.zeros(shape + (4,), np.float32)
+        segments = ctypes.c_uint64(0)
+        self._call("rt_lens", ctypes.c_void_p(cam.ctypes.data), first, count, N.ptr(out), *scalars, ctypes.byref(segments))
+        return (out, segments.value) if return_segments else out
+
+    def lens_rays(self, cam, sample_index: int = 1, region=None, device: bool = False):
+        """The rays ``lens`` starts the paths of sample ``sample_index`` with (rt_lens_rays): a
+        ``buffers.RADIANCE_RAY`` array of shape (h, w), or (count,) with ``region``, which
+        ``radiance(rays, first_sample=sample_index, samples=1)`` answers with the bits of
+        ``lens(first_sample=sample_index, samples=1)``. With ``device`` a CUDA float32 tensor of
+        shape (..., 8) (rt_lens_rays_device), which ``radiance`` takes as it is once flattened."""
+        cam, first, count, shape = self._lens_range(cam, region)
+        if device:
+            return self._lens_device("rt_lens_rays_device", cam, first, count, shape + (8,), (int(sample_index),), None)
+        out = np.zeros(shape, B.RADIANCE_RAY)
+        self._call("rt_lens_rays", ctypes.c_void_p(cam.ctypes.data), first, count, int(sample_index), N.ptr(out))
+        return out
+
+    def _lens_device(self, entry, cam, first, count, shape, scalars, segments):
+        """The device form of a lens entry point into a new CUDA float32 tensor of ``shape``.
+        ``segments``: None for an entry without a segments argument, else whether to count them."""
+        import torch
+
+        dev = torch.device(f"cuda:{self.device}")
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        counter = torch.zeros(1, dtype=torch.int64, device=dev) if segments else None
+        args = [ctypes.c_void_p(cam.ctypes.data), first, count]
+        result = ctypes.c_void_p(out.data_ptr() if count else None)
+        if segments is None:  # rt_lens_rays_device(cam, first, count, sample_index, rays)
+            args += [*scalars, result]
+        else:
+            args += [result, *scalars, ctypes.c_void_p(counter.data_ptr()) if segments else None]
+        mine = torch.cuda.ExternalStream(self.stream_handle, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        mine.wait_stream(cur)  # (the ordering of _device_query)
+        self._call(entry, *args)
+        cur.wait_stream(mine)
+        return (out, int(counter.item())) if segments else out
+
     # ------------------------------------------------------------------ feature buffers & denoiser
     def compute_features(self) -> None:
         """rt_compute_features: the first-hit feature planes, recomputed only after a camera or

@@ -2,6 +2,7 @@
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
                                    [--reps 20] [--sweep] [--occluded] [--radiance] [--gather] [--probe] [--ambient]
+                                   [--lens]
                                    [--out profiles/query_bench.jsonl]
 
 Rays: the configuration's width x height camera rays (coherent: neighbouring rays are
@@ -65,6 +66,14 @@ leaves out the transfer of 32 B per sample that a caller would pay. Each round c
 open counts of (a) equal samples minus the sums of (c)'s bytes, and that the contract's tree over
 (c)'s terms equals (a) bit for bit. Device events on the context's stream; median, minimum and
 maximum over --rounds.
+--lens: the lens query (rt_lens_device) against the radiance query of the same rays, in one process
+(DESIGN.md §5.4l). The pinhole descriptor of the configuration's camera (stream_base 0: the frame's
+own samples) at samples = 1, next to rt_radiance_device on the host-built records of the same rays
+(camera origin, each pixel's direction, stream = pixel index), which is the parent's code; and a thin
+lens (aperture 0.3, focused at 10) next to rt_lens_rays_device followed by rt_radiance_device on its
+records. A round runs `reps` calls of each series with first_sample = 1 .. reps; each pair is checked
+to return the same bits and the same segments. Device events on the context's stream; median, minimum
+and maximum milliseconds per call over --rounds rounds after --settle-ms of untimed work.
 Prints one JSON line per measurement (and appends them to --out).
 """
 import argparse
@@ -256,6 +265,79 @@ def radiance_bench(r, args, scene, bounces, dev, emit):
          ratio=round(med(rad_rate) / med(frame_rate), 3),
          closest_hit_ms=round(med(hit_ms), 4), closest_hit_mray_s=round(n / med(hit_ms) / 1e3, 1),
          closest_hit_ratio=round(n / med(hit_ms) / 1e3 / med(frame_rate), 3), build=r._lib.rt_build_hash().decode())
+
+
+def lens_bench(r, args, scene, bounces, dev, emit):
+    """The --lens series (module docstring)."""
+    import statistics
+
+    import torch
+
+    from rust_gpu_raytracing_amd.camera import lens_camera
+
+    d = scene.camera.recalculate_ray_directions()["direction"]
+    n = d.shape[0]
+    q = np.zeros(n, B.RADIANCE_RAY)
+    q["origin"] = np.asarray(scene.camera.position, np.float32)
+    q["direction"] = d
+    q["stream"] = np.arange(n, dtype=np.uint32)
+    records_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    drawn_t = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out_t = {k: torch.empty((n, 4), dtype=torch.float32, device=dev) for k in ("lens", "records")}
+    seg_t = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in ("lens", "records")}
+    torch.cuda.synchronize()  # uploaded on torch's stream, read on the context's
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+    cams = {"pinhole": np.ascontiguousarray(lens_camera(scene.camera).reshape(1)),
+            "thin_lens": np.ascontiguousarray(lens_camera(scene.camera, aperture=0.3, focus=10.0, stream_base=1).reshape(1))}
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+    def lens(cam, u):
+        r._call("rt_lens_device", ctypes.c_void_p(cam.ctypes.data), 0, n, P(out_t["lens"]), bounces, u, 1, P(seg_t["lens"]))
+
+    def radiance(rays_t, u):
+        r._call("rt_radiance_device", P(rays_t), P(out_t["records"]), n, bounces, u, 1, P(seg_t["records"]))
+
+    def drawn(cam, u):  # what a caller of the parent would have had to build on the host, per sample
+        r._call("rt_lens_rays_device", ctypes.c_void_p(cam.ctypes.data), 0, n, u, P(drawn_t))
+        radiance(drawn_t, u)
+
+    series = {"pinhole/lens": lambda u: lens(cams["pinhole"], u),
+              "pinhole/records": lambda u: radiance(records_t, u),
+              "thin_lens/lens": lambda u: lens(cams["thin_lens"], u),
+              "thin_lens/rays_then_records": lambda u: drawn(cams["thin_lens"], u)}
+    same = {}
+    for camera in cams:  # what is timed is the same computation
+        names = [k for k in series if k.startswith(camera + "/")]
+        for t in seg_t.values():
+            t.zero_()
+        torch.cuda.synchronize()
+        for k in names:
+            series[k](2)
+        r.synchronize()
+        same[camera] = bool(torch.equal(out_t["lens"].view(torch.int32), out_t["records"].view(torch.int32)))
+        assert same[camera] and int(seg_t["lens"].item()) == int(seg_t["records"].item()) > 0, (camera, same)
+    t_settle = time.perf_counter()
+    while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
+        for f in series.values():
+            f(1)
+        r.synchronize()
+    ms = {k: [] for k in series}
+    for _ in range(args.rounds):
+        for k, f in series.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            for i in range(args.reps):
+                f(1 + i)
+            t1.record(stream)
+            t1.synchronize()
+            ms[k].append(t0.elapsed_time(t1) / args.reps)
+    med = statistics.median
+    for k, v in ms.items():
+        camera, name = k.split("/")
+        emit(kind="lens", camera=camera, series=name, bounces=bounces, pixels=n, samples=1, rounds=args.rounds,
+             reps=args.reps, ms=round(med(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4),
+             spread=round((max(v) - min(v)) / med(v), 4), ratio_to_lens=round(med(v) / med(ms[camera + "/lens"]), 4),
+             bit_identical=same[camera], build=r._lib.rt_build_hash().decode())
 
 
 def build_gather_records():
@@ -660,6 +742,7 @@ def main():
     ap.add_argument("--probe", action="store_true", help="the probe query against the same paths done by hand")
     ap.add_argument("--ambient", action="store_true",
                     help="the ambient query against the gather at one bounce and the resident occlusion records")
+    ap.add_argument("--lens", action="store_true", help="the lens query against the radiance query of the same rays")
     ap.add_argument("--ambient-configs", default="c2_rtiow,c3_chess", help="--ambient: the configurations, in one process")
     ap.add_argument("--t-max", type=float, default=1.0, help="--ambient: the bound of every point, in world units")
     ap.add_argument("--points", type=int, default=None,
@@ -667,7 +750,7 @@ def main():
     ap.add_argument("--samples", type=int, default=None,
                     help="--gather, --probe: samples per point (1024); --ambient: samples per point (256)")
     ap.add_argument("--bounces", type=int, default=None,
-                    help="--radiance, --gather, --probe: bounce limit (default: the configuration's)")
+                    help="--radiance, --gather, --probe, --lens: bounce limit (default: the configuration's)")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="--radiance: untimed work before the rounds")
     ap.add_argument("--rounds", type=int, default=7, help="--occluded, --radiance: rounds the series alternate over")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
@@ -710,7 +793,9 @@ def main():
         lines_out(args, lines)
         return
     with Renderer(scene, tuning=tuning) as r:
-        if args.probe:
+        if args.lens:
+            lens_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
+        elif args.probe:
             probe_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
         elif args.gather:
             gather_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
