@@ -1420,7 +1420,8 @@ RT_API int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value);
 RT_API int rt_set_tile_schedule(rt_ctx* ctx, uint32_t schedule);
 /* The claim order the next launch uses (order[q] = local tile claimed at
  * queue position q; the identity when none is sorted yet) and the rays per
- * tile recorded by the last launch (zero once a later launch sorted them).
+ * tile recorded by the last launch (zero once a later launch sorted them;
+ * a frame-parallel batch records the rays of its first frame only).
  * Either pointer may be NULL; each holds the rank's owned tile count
  * (rt_owned_pixel_count / 64). Synchronous. */
 RT_API int rt_tile_schedule_state(rt_ctx* ctx, uint32_t* order, uint32_t* costs);

@@ -382,6 +382,17 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
             l_aux[2u * i + 1u] = make_float4(c.x, c.y, c.z, c.w);
         }
         sv.mat_aux = l_aux;
+        // the environment line (rt_kernel_args.h): decode_texel of the texels sample_env fetches, down
+        // column 0 (rows uniform), along row 0 (columns uniform), or texel 0 alone (both)
+        if (ka.env_uniform & kEnvLineStaged) {
+            float4* l_env = reinterpret_cast<float4*>(l_srgb) + kLdsTailBytes / sizeof(float4);
+            const uint32_t n = env_line_texels(ka.env_uniform, ka.env_w, ka.env_h);
+            const size_t stride = (ka.env_uniform & 2u) ? 1u : ka.env_w;
+            for (uint32_t i = tid; i < n; i += kThreads) {
+                const f4 c = decode_texel(ka.env[(size_t)i * stride], ka.srgb);
+                l_env[i] = make_float4(c.x, c.y, c.z, c.w);
+            }
+        }
         if constexpr (kTris)
             for (uint32_t i = tid; i < ka.object_count; i += kThreads) l_obj[i] = ka.objects[i];
         sv.sph = l_sph;
@@ -586,10 +597,10 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
             uint32_t bounce_limit;
             if constexpr (kFramePar) {
                 const ShadeArgs sa = load_shade_args(kernarg_fresh(kernarg));
-                ended = shade<(kMode >= 1)>(sv, sa, p, h);
+                ended = shade<(kMode >= 1), (kMode >= 1)>(sv, sa, p, h);
                 bounce_limit = sa.bounces;
             } else {
-                ended = shade<(kMode >= 1)>(sv, ka, p, h);
+                ended = shade<(kMode >= 1), (kMode >= 1)>(sv, ka, p, h);
                 bounce_limit = ka.bounces;
             }
             if (ended) {
@@ -601,7 +612,9 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                 mode = kSetup;
             }
         }
-        if (ka.tile_cost) record_tile_cost(ka.tile_cost, fin, lane_tile, fin_rays);
+        // (a frame-parallel batch traces every tile once per frame: the sort needs the tiles' relative
+        // order only, so the batch's first frame alone is recorded and most passes record nothing)
+        if (ka.tile_cost) record_tile_cost(ka.tile_cost, fin && (!frame_par || frame == 0u), lane_tile, fin_rays);
 #ifdef RT_DIAG
         const unsigned long long ts1 = stamp();
         shade_cyc += ts1 - ts0;

@@ -224,8 +224,9 @@ struct rt_ctx {
     // context whose launches alternate instances (full batches and a one-frame remainder) asks once each
     struct OccEntry {
         size_t lds_bytes = 0, stack_pt = 0;
+        size_t line_bytes = 0;  // the environment line asked for; env_line: the same configuration holds it
         int mode = -1, blocks_per_cu = 0;
-        bool tris = false;
+        bool tris = false, env_line = false;
         uint32_t threads = 0, force_threads = 0, waves_cap = 0;
     } occ_cache[2];
     size_t occ_stack_pt = 0;
@@ -1597,14 +1598,33 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     const size_t lane_pt = coop ? (size_t)kLeafBatchWaveBytes / 64u : 0u;
     // Persistent grid: as many workgroups as can be resident (never more than
     // one wave per tile); waves then pull tiles from the queue.
+    // The environment line (rt_kernel_args.h): the decoded texels of a rows- or columns-uniform
+    // environment map, staged after the scene image's tail by the instances that stage the scene.
+    size_t line_bytes = 0;
+    if (mode >= 1) {
+        const uint32_t n = env_line_texels(ka.env_uniform, ka.env_w, ka.env_h);
+        if (n != 0 && n <= kEnvLineMax) line_bytes = (size_t)n * sizeof(float4);
+    }
     rt_ctx::OccEntry& oc = ctx->occ_cache[fp_instance ? 1 : 0];
     if (oc.blocks_per_cu == 0 || oc.lds_bytes != lds_bytes || oc.mode != mode || oc.tris != tris ||
-        oc.stack_pt != lane_pt || oc.force_threads != ctx->force_threads || oc.waves_cap != ctx->waves_cap) {
+        oc.stack_pt != lane_pt || oc.force_threads != ctx->force_threads || oc.waves_cap != ctx->waves_cap ||
+        oc.line_bytes != line_bytes) {
         int per_cu = 0;
         uint32_t threads = 0;
         hipError_t oe = rt_pathtrace_pick_config(mode, tris, fp_instance, lds_bytes, lane_pt, ctx->force_threads,
                                                  ctx->waves_cap, &threads, &per_cu);
         if (oe != hipSuccess) return hip_fail(ctx, "rt_pathtrace_pick_config (occupancy query)", oe);
+        // the line is staged only where the launch keeps its workgroup size and its workgroups per CU with it
+        oc.env_line = false;
+        if (line_bytes != 0) {
+            int per_cu_line = 0;
+            uint32_t threads_line = 0;
+            oe = rt_pathtrace_pick_config(mode, tris, fp_instance, lds_bytes + line_bytes, lane_pt, ctx->force_threads,
+                                          ctx->waves_cap, &threads_line, &per_cu_line);
+            if (oe != hipSuccess) (void)hipGetLastError();  // no configuration holds it: the global path
+            oc.env_line = oe == hipSuccess && threads_line == threads && per_cu_line == per_cu;
+        }
+        oc.line_bytes = line_bytes;
         oc.blocks_per_cu = per_cu;
         oc.threads = threads;
         oc.lds_bytes = lds_bytes;
@@ -1621,7 +1641,11 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     ctx->occ_mode = mode;
     ctx->occ_tris = tris;
     ctx->occ_stack_pt = lane_pt;
-    // the leaf batch scratch after the scene image and its tail
+    if (oc.env_line) {  // right after the tail (a multiple of 16 bytes, as the image before it)
+        ka.env_uniform |= kEnvLineStaged;
+        lds_bytes += line_bytes;
+    }
+    // the leaf batch scratch after the scene image, its tail and the environment line
     ka.lds_leafbatch_offset = (uint32_t)al16(lds_bytes);
     if (coop) lds_bytes = ka.lds_leafbatch_offset + (size_t)ctx->occ_threads * lane_pt;
     const uint32_t waves_per_block = ctx->occ_threads / 64;

@@ -93,6 +93,27 @@ constexpr uint32_t kOrderBuckets = RT_ORDER_BUCKETS;
 constexpr size_t kLdsTailBytes = 1024 + 160;
 static_assert(kLdsTailBytes >= (kOrderBuckets * 16 + 1) * 4, "sort scratch fits the LDS tail");
 
+// The environment line (path kernel, modes 1 and 2): when the environment map's rows, or
+// columns, are each one colour, the texel a miss fetches depends on one coordinate only, and the
+// workgroup stages the decoded texels of that line -- one float4 per row (column), one entry when
+// both hold -- in LDS right after the tail (not in it: the tail is shared with the query kernels
+// and the sort's scratch and must not grow). The host sets kEnvLineStaged in KernelArgs::env_uniform
+// for a launch that has room for it; lines longer than kEnvLineMax texels (8 KiB: RTIOW's
+// 512-row sky fits, and the mode-2 budget plus the line stays within the LDS of a CU) stay in
+// global memory.
+constexpr uint32_t kEnvLineMax = 512;
+constexpr uint32_t kEnvLineStaged = 4u;
+static_assert(kLdsTailBytes % 16 == 0, "the environment line after the tail is 16-byte aligned");
+// Texels of the line for env_uniform bits 0 (rows uniform) and 1 (columns uniform); 0: no line.
+__host__ __device__ inline uint32_t env_line_texels(uint32_t env_uniform, uint32_t env_w, uint32_t env_h) {
+    switch (env_uniform & 3u) {
+        case 3u: return 1u;
+        case 1u: return env_h;
+        case 2u: return env_w;
+        default: return 0u;
+    }
+}
+
 // Cooperative leaf batches (pathtrace.hip coop_leaf_batch): a leaf record's triangle block, and
 // the per-wave LDS scratch (one 48-B slot per lane: the ray and leaf of a pending lane, then its
 // leaf's result).
@@ -232,7 +253,8 @@ struct KernelArgs {
     uint32_t triangle_count;
     uint32_t tex_w, tex_h, tex_layers;
     uint32_t env_w, env_h;
-    uint32_t env_uniform;  // bit 0: env map rows uniform (u unused), bit 1: columns uniform (v unused)
+    uint32_t env_uniform;  // bit 0: env map rows uniform (u unused), bit 1: columns uniform (v unused);
+                           // kEnvLineStaged (path kernel only): the decoded line is in LDS after the tail
     // launch geometry
     uint32_t height;
     uint32_t bounces;

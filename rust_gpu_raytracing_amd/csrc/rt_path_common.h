@@ -416,7 +416,13 @@ __device__ __forceinline__ uint32_t fetch_texture(const KA& ka, uint32_t layer, 
     return ka.textures[off];
 }
 
-template <class KA>
+// kLine (the path kernel's instances that stage the scene): when the launch staged the
+// environment line (rt_kernel_args.h, kEnvLineStaged) the texel is read from it -- the same
+// coordinates, and line[] holds decode_texel of the texel fetched for them: rows uniform, the texel
+// of column 0 in row y; columns uniform, of row 0 in column x; both, texel 0. At most one coordinate
+// is computed then, so the entry is x + y: no global load and no decode. The line follows the
+// LDS tail that `srgb` starts.
+template <bool kLine = false, class KA>
 __device__ __forceinline__ f4 sample_env(const KA& ka, const float* srgb, f3 d) {
     // environment_map_coords, :580-585. A coordinate is computed only when the
     // texel depends on it: with every row (column) of the map one colour, any u
@@ -429,6 +435,10 @@ __device__ __forceinline__ f4 sample_env(const KA& ka, const float* srgb, f3 d) 
     if (!(ka.env_uniform & 2u)) {
         const float v = 0.5f + div_const(asinf_c(d.y), kWgslPi, kInvWgslPi);
         y = texel_coord(v * (float)(int32_t)ka.env_map_height, ka.env_h);
+    }
+    if (kLine && (ka.env_uniform & kEnvLineStaged)) {
+        const float4 c = (reinterpret_cast<const float4*>(srgb) + kLdsTailBytes / sizeof(float4))[x + y];
+        return f4{c.x, c.y, c.z, c.w};
     }
     return decode_texel(ka.env[(size_t)y * ka.env_w + (size_t)x], srgb);
 }
@@ -508,10 +518,12 @@ __device__ __forceinline__ void start_sample_at(f3 origin, uint32_t stream, uint
 // environment, or the bounce limit is reached).
 // kAux: the material's glass constants come from the LDS table staged with the
 // materials (same f32 operations, computed once per workgroup instead of per hit).
-template <bool kAux, class KA>
+// kEnvLine: a miss may read its texel from the environment line (sample_env<true>); every
+// other caller keeps sample_env's global load.
+template <bool kAux, bool kEnvLine = false, class KA>
 __device__ __forceinline__ bool shade(const SceneView& sv, const KA& ka, Path& p, const Hit& h) {
     if (h.t == kF32Max) {
-        const f4 c = sample_env(ka, sv.srgb, p.d);
+        const f4 c = sample_env<kEnvLine>(ka, sv.srgb, p.d);
         p.light.x = p.light.x + c.x * p.contrib.x;
         p.light.y = p.light.y + c.y * p.contrib.y;
         p.light.z = p.light.z + c.z * p.contrib.z;
