@@ -297,6 +297,16 @@ struct WalkStepCount {
 };
 #endif
 
+// The sphere-only instances that stage the scene walk the linked form of the sphere BVH
+// (rt_sphere_walk.h): staging rewrites the nodes and writes the sentinel after them.
+template <int kMode, bool kTris>
+constexpr bool kLinkedWalk = kBlockLeaves<kTris> && kMode >= 1;
+
+// The LDS address of an object in LDS (what a ds_read takes).
+__device__ __forceinline__ uint32_t lds_address(const void* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+
 // Dynamic LDS image, in this order (all 16-byte aligned):
 //   float4   sphere slots[sphere_count]   centre.xyz, radius^2
 //   RtMaterial materials[material_count]
@@ -304,6 +314,7 @@ struct WalkStepCount {
 //   uint32   slot -> original index[sphere_count]
 //   uint32   sphere material[sphere_count] (by original index)
 //   float4x2 sphere BVH nodes[sphere_nodes]
+//   float4x2 the sphere walk's sentinel                 (sphere-only scenes)
 //   float4x2 triangle accelerator nodes[tri_nodes]      (mode 2)
 //   uint4    triangle accelerator leaves[tri_prims]     (mode 2)
 //   float    srgb[256]
@@ -365,7 +376,15 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
             l_orig[i] = ka.sphere_orig[i];
         }
         for (uint32_t i = tid; i < ka.sphere_count; i += kThreads) l_smat[i] = ka.sphere_material[i];
-        for (uint32_t i = tid; i < 2u * ka.sphere_nodes; i += kThreads) l_nodes[i] = ka.sphere_bvh[i];
+        if constexpr (kLinkedWalk<kMode, kTris>) {
+            // the linked form of the nodes and the sentinel after them (rt_sphere_walk.h)
+            const uint32_t base = lds_address(l_nodes);
+            for (uint32_t i = tid; i < 2u * ka.sphere_nodes; i += kThreads)
+                l_nodes[i] = sphere_links_stage(ka.sphere_bvh[i], i, base, ka.sphere_nodes);
+            if (tid < 2u) l_nodes[2u * ka.sphere_nodes + tid] = sphere_links_sentinel<float4>(tid, base, ka.sphere_nodes);
+        } else {
+            for (uint32_t i = tid; i < 2u * ka.sphere_nodes; i += kThreads) l_nodes[i] = ka.sphere_bvh[i];
+        }
         float4* l_aux = reinterpret_cast<float4*>(lds + ka.lds_mat_aux_offset);
         for (uint32_t i = tid; i < ka.material_count; i += kThreads) {
             const RtMaterial m = ka.materials[i];
@@ -426,6 +445,12 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 
     const bool accumulate = kFramePar || ka.accumulate == 1u;
     const uint32_t samples = accumulate ? ka.compute_per_frame : 1u;  // :158-175
+    // The sphere walk's first node and its end: LDS addresses, the end the sentinel's, in the
+    // instances that stage the linked form (rt_sphere_walk.h); else index 0 and the node count.
+    constexpr bool kLinked = kLinkedWalk<kMode, kTris>;
+    const uint32_t walk_base = kLinked ? lds_address(lds + ka.lds_nodes_offset) : 0u;
+    const uint32_t walk_end = kLinked ? sphere_links_addr(walk_base, ka.sphere_nodes) : ka.sphere_nodes;
+    const auto walk_over = [&](uint32_t node) { return kLinked ? node == walk_end : node >= walk_end; };
 
     // Lane states. A lane owns one pixel at a time and one ray of its path.
     constexpr uint32_t kIdle = 0, kSetup = 1, kTrav = 2, kDone = 3, kPrimary = 4;
@@ -678,6 +703,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                 while (mode == kSetup && p.bounce >= ka.bounces) finish_sample();
             if (kFramePar || mode == kSetup) {
                 trace_begin<kTris>(sv, ka, p.o, p.d, ts);
+                if constexpr (kLinkedWalk<kMode, kTris>) ts.node = sphere_links_addr(walk_base, ts.node);
                 mode = ts.phase == 2 ? kDone : kTrav;
             }
         }
@@ -760,14 +786,24 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
                     const SphereWalkNoHook hook{};
 #endif
                     constexpr int kSteps = kTravUnroll<kMode, kTris>;
-                    if (ka.sphere_boxes_ordered)
-                        sphere_walk_block<kSteps, true>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit, ts.node,
-                                                        ts.pending, hook);
-                    else
-                        sphere_walk_block<kSteps, false>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit, ts.node,
-                                                         ts.pending, hook);
+                    // (ts.node and walk_end: node addresses in the instances that stage the linked form)
+                    if constexpr (kLinkedWalk<kMode, kTris>) {
+                        if (ka.sphere_boxes_ordered)
+                            sphere_links_block<kSteps, true, float4>(lds, walk_end, ts.slab, ts.slack, ts.limit, ts.node,
+                                                                     ts.pending, hook);
+                        else
+                            sphere_links_block<kSteps, false, float4>(lds, walk_end, ts.slab, ts.slack, ts.limit, ts.node,
+                                                                      ts.pending, hook);
+                    } else {
+                        if (ka.sphere_boxes_ordered)
+                            sphere_walk_block<kSteps, true>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit,
+                                                            ts.node, ts.pending, hook);
+                        else
+                            sphere_walk_block<kSteps, false>(sv.nodes, ka.sphere_nodes, ts.slab, ts.slack, ts.limit,
+                                                             ts.node, ts.pending, hook);
+                    }
                     RT_ISA_MARK("walk_block_end");
-                    if (ts.pending == kNoLeaf && ts.node >= ka.sphere_nodes) {
+                    if (ts.pending == kNoLeaf && walk_over(ts.node)) {
                         ts.phase = 2;
                         mode = kDone;
                     }
@@ -793,7 +829,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 #endif
                         ts.limit = prune_limit(ts);
                         ts.pending = kNoLeaf;
-                        if (ts.node >= ka.sphere_nodes) {
+                        if (walk_over(ts.node)) {
                             ts.phase = 2;
                             mode = kDone;
                         }

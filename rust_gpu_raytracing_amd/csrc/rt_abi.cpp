@@ -1287,6 +1287,11 @@ static int scene_carve_layouts(rt_ctx* ctx, KernelArgs& ka, uint32_t layouts, si
     off = al16(off + (size_t)p.sphere_count * 4);
     ka.lds_nodes_offset = (uint32_t)off;
     off = al16(off + (size_t)layouts * ctx->n_nodes * sizeof(SphereBvhNode));
+    // sphere-only scenes: one more record, the sentinel that ends the path kernel's walk
+    // (rt_sphere_walk.h). Every kernel that lays out its image here (the query, occlusion, radiance,
+    // ambient and lens kernels, which neither write nor read it) inherits the 32 bytes, also where
+    // this decides between eight layouts and one or between placement modes.
+    if (p.object_count == 0) off += sizeof(SphereBvhNode);
     sl.mode1_bytes = off + kLdsTailBytes;
     ka.lds_tri_nodes_offset = (uint32_t)off;
     off = al16(off + (size_t)ka.tri_nodes * sizeof(SphereBvhNode));
