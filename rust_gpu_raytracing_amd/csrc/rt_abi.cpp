@@ -18,6 +18,7 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -176,7 +177,7 @@ struct rt_ctx {
     uint32_t pending_bounces = 0;
     bool frame_parallel = true;     // tuning "frame_parallel" 0: batches run frames back to back per lane
     float4* d_frame_light[2] = {};    // frame-parallel batch lights (by batch parity), owned px x frames x samples
-    size_t frame_light_cap = 0;       // float4 entries, each
+    size_t frame_light_cap = 0;       // bytes, each
     // overlapped batches (dispatch_frames): batch i runs on streams[i % 2]
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_resolved[2] = {};   // after batch i's resolve (i % 2)
@@ -196,7 +197,7 @@ struct rt_ctx {
     bool derived_octants = false, derived_qnodes = false;  // what the last derivation produced
     uint4* d_tri_qnodes = nullptr;
     float4* d_tri_qgrid = nullptr;
-    size_t qnodes_cap = 0;
+    size_t qnodes_cap = 0;  // bytes
     bool batch_schedule = false;      // tuning "batch_schedule" 1: cost-ordered claims in batches too
     // tuning "frame_par_instance" 0: frame-parallel batches run the generic path kernel instance too
     bool frame_par_instance = true;
@@ -217,22 +218,21 @@ struct rt_ctx {
     uint32_t queue_stripes = kQueueStripes;  // tuning "queue_stripes"
     int n_cu = 0;
     bool force_global_scene = false;   // tuning "scene_in_lds" 0
-    size_t occ_lds_bytes = 0;
-    int occ_mode = -1;
-    bool occ_tris = false;
     // the occupancy query's answer per path kernel instance (0 generic, 1 frame-parallel), so that a
     // context whose launches alternate instances (full batches and a one-frame remainder) asks once each
-    struct OccEntry {
+    struct OccKey {  // what the answer depends on (no padding: same_key compares the bytes)
         size_t lds_bytes = 0, stack_pt = 0;
         size_t line_bytes = 0;  // the environment line asked for; env_line: the same configuration holds it
-        int mode = -1, blocks_per_cu = 0;
-        bool tris = false, env_line = false;
-        uint32_t threads = 0, force_threads = 0, waves_cap = 0;
+        int mode = -1;
+        uint32_t tris = 0, force_threads = 0, waves_cap = 0;
+    };
+    struct OccEntry {
+        OccKey key;
+        int blocks_per_cu = 0;
+        uint32_t threads = 0;
+        bool env_line = false;
     } occ_cache[2];
-    size_t occ_stack_pt = 0;
     int max_lds_mode = 2;               // tuning "lds_mode": highest staging mode allowed
-    int occ_blocks_per_cu = 0;
-    uint32_t occ_threads = 0;
     uint32_t force_threads = 0;        // tuning "block_threads"; 0 = pick by occupancy
     uint32_t waves_cap = 0;            // tuning "waves_per_cu"; 0 = default cap
     uint32_t trav_threshold = 0;  // tuning "trav_threshold"; 0 = by scene (trav_threshold_for)
@@ -246,7 +246,10 @@ struct rt_ctx {
     // per stream (launches on the auxiliary stream keep their own history):
     uint32_t* d_tile_sched[2] = {};    // costs[2][n], orders[2][n], flags[2] (n = owned tiles)
     uint64_t sched_launches[2] = {};   // launches since the schedule was (re)set
-    uint32_t last_blocks = 0, last_lds = 0;
+    // the last launch (rt_launch_config): workgroups, dynamic LDS, workgroup size, and the
+    // placement mode of the last path kernel launch (-1: none yet)
+    uint32_t last_blocks = 0, last_lds = 0, last_threads = 0;
+    int last_mode = -1;
     uint32_t last_passes = 0;  // RT_PASS_* of the last dispatch
     float4* d_slot_sph = nullptr;        // kernel-ordered spheres (sphere_bvh.h)
     uint32_t* d_slot_orig = nullptr;
@@ -315,7 +318,7 @@ struct rt_ctx {
     // C5 5.02 -> 4.93 ms (profiles/r03_al/ab_c5_ptm.jsonl); tuning "primary_tile_major" 0: frame-major
     bool primary_tile_major = true;
     uint4* d_primary[2] = {};   // per batch parity (overlapped batches), owned px x frames x samples records
-    size_t primary_cap = 0;
+    size_t primary_cap = 0;     // bytes, each
     // sub-object bytes of the brute-force launches: [0] SURVEY §8d's tile-streaming convention,
     // [1] what the sweeps read from L2
     unsigned long long* d_stream = nullptr;
@@ -397,11 +400,11 @@ struct rt_ctx {
     size_t probe_lights_bytes = 0;
     unsigned long long* d_probe_next = nullptr;     // the chunk counters of the two launches in flight
     uint4* d_lens_cam = nullptr;                    // rt_lens: the descriptor the launches of a call read
-    int q_occ_mode = -1;                        // occupancy of the last query instance
-    int q_occ_kind = 0;                         // (which kernel's: QueryKind)
-    bool q_occ_tris = false;
-    size_t q_occ_lds = 0;
-    int q_occ_blocks = 0;
+    struct QueryOccKey {                        // the last query instance (kind: which kernel's, QueryKind)
+        int mode = -1, kind = 0;
+        uint32_t tris = 0, lds_bytes = 0;
+    } q_occ_key;
+    int q_occ_blocks = 0;                       // its resident workgroups per CU
 
     // first-hit feature buffers and the denoiser (rt_compute_features, rt_denoise; denoise.hip).
     // scene_epoch counts the calls that can change what a camera ray hits or what it looks up
@@ -470,6 +473,38 @@ int hip_fail(rt_ctx* ctx, const char* what, hipError_t e) {
         hipError_t e_ = (call);                          \
         if (e_ != hipSuccess) return hip_fail(ctx, #call, e_); \
     } while (0)
+
+// A device buffer of at least `bytes` -- or `n` of them under one capacity: the pairs by batch
+// parity -- reallocated when smaller, after both streams have drained: nothing may still read
+// it. The capacity stays 0 until every allocation has succeeded. `what` names the buffer in the
+// out-of-memory message; *stale is set when it was reallocated (what the caller derived into it
+// is gone).
+template <typename T>
+int grow_buffer(rt_ctx* ctx, const char* what, T** p, size_t* cap, size_t bytes, bool* stale = nullptr, size_t n = 1) {
+    if (p[0] && *cap >= bytes) return RT_OK;
+    RT_HIP(ctx, join_aux(ctx));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) {
+        if (p[i]) RT_HIP(ctx, hipFree(p[i]));
+        p[i] = nullptr;
+    }
+    *cap = 0;
+    const size_t alloc = bytes < 256 ? 256 : bytes;
+    for (size_t i = 0; i < n; i++) {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p[i]), alloc);
+        if (e != hipSuccess) return fail(ctx, RT_E_NOMEM, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    *cap = alloc;
+    if (stale) *stale = true;
+    return RT_OK;
+}
+
+// Cache keys are plain structs without padding, compared as a whole.
+template <typename K>
+bool same_key(const K& a, const K& b) {
+    static_assert(std::has_unique_object_representations_v<K>, "the key's bytes must be its value");
+    return std::memcmp(&a, &b, sizeof(K)) == 0;
+}
 
 // A caller's device pointer, as an entry point requires it.
 struct DevicePtr {
@@ -615,23 +650,12 @@ int refresh_tri_accel(rt_ctx* ctx, uint32_t object_count) {
     if (!ctx->tri_dirty && ctx->tri_count_built == object_count) return RT_OK;
     int rc0 = sync_host_geometry(ctx);
     if (rc0) return rc0;
-    auto ensure = [&](void** p, size_t* cap, size_t bytes) -> int {
-        if (bytes <= *cap && *p) return RT_OK;
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (*p) RT_HIP(ctx, hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-        const size_t alloc = bytes < 256 ? 256 : bytes;
-        RT_HIP(ctx, hipMalloc(p, alloc));
-        *cap = alloc;
-        return RT_OK;
-    };
     int rc;
     TriangleAccel acc;
     build_triangle_accel(ctx->h_obj.data(), object_count, ctx->h_sub.data(), (uint32_t)ctx->h_sub.size(), &acc);
     const size_t nb = acc.nodes.size() * sizeof(SphereBvhNode), pb = acc.prims.size() * sizeof(SubObjectPrim);
-    if ((rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_bvh), &ctx->tri_bvh_cap, nb)) ||
-        (rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_prims), &ctx->tri_prims_cap, pb)) ||
+    if ((rc = grow_buffer(ctx, "triangle accelerator nodes", &ctx->d_tri_bvh, &ctx->tri_bvh_cap, nb)) ||
+        (rc = grow_buffer(ctx, "triangle accelerator leaves", &ctx->d_tri_prims, &ctx->tri_prims_cap, pb)) ||
         (rc = upload_raw(ctx, ctx->d_tri_bvh, acc.nodes.data(), nb)) ||
         (rc = upload_raw(ctx, ctx->d_tri_prims, acc.prims.data(), pb)))
         return rc;
@@ -648,9 +672,9 @@ int refresh_tri_accel(rt_ctx* ctx, uint32_t object_count) {
         std::vector<uint32_t> skip(oct.size());
         for (size_t i = 0; i < oct.size(); i++) skip[i] = oct[i].skip;
         const size_t b8 = oct.size() * 4;
-        if ((rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_src8), &ctx->tri_src8_cap, b8)) ||
-            (rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_skip8), &ctx->tri_skip8_cap, b8)) ||
-            (rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_bvh8), &ctx->tri_bvh8_cap, oct.size() * sizeof(SphereBvhNode))) ||
+        if ((rc = grow_buffer(ctx, "octant layout sources", &ctx->d_tri_src8, &ctx->tri_src8_cap, b8)) ||
+            (rc = grow_buffer(ctx, "octant layout links", &ctx->d_tri_skip8, &ctx->tri_skip8_cap, b8)) ||
+            (rc = grow_buffer(ctx, "octant layout nodes", &ctx->d_tri_bvh8, &ctx->tri_bvh8_cap, oct.size() * sizeof(SphereBvhNode))) ||
             (rc = upload_raw(ctx, ctx->d_tri_src8, src.data(), b8)) ||
             (rc = upload_raw(ctx, ctx->d_tri_skip8, skip.data(), b8)))
             return rc;
@@ -671,8 +695,8 @@ int refresh_tri_accel(rt_ctx* ctx, uint32_t object_count) {
     for (size_t l = 1; l < off.size(); l++) off[l] += off[l - 1];
     std::vector<uint32_t> fill(off.begin(), off.end() - 1);
     for (size_t i = 0; i < acc.nodes.size(); i++) order[fill[max_depth - depth[i]]++] = (uint32_t)i;
-    if ((rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_order), &ctx->tri_order_cap, order.size() * 4)) ||
-        (rc = ensure(reinterpret_cast<void**>(&ctx->d_tri_level_off), &ctx->tri_level_cap, off.size() * 4)) ||
+    if ((rc = grow_buffer(ctx, "refit order", &ctx->d_tri_order, &ctx->tri_order_cap, order.size() * 4)) ||
+        (rc = grow_buffer(ctx, "refit levels", &ctx->d_tri_level_off, &ctx->tri_level_cap, off.size() * 4)) ||
         (rc = upload_raw(ctx, ctx->d_tri_order, order.data(), order.size() * 4)) ||
         (rc = upload_raw(ctx, ctx->d_tri_level_off, off.data(), off.size() * 4)) ||
         (rc = upload_raw(ctx, ctx->d_tri_extent, &acc.extent, 4)))
@@ -744,21 +768,6 @@ int dev_alloc(rt_ctx* ctx, T** p, size_t count) {
     return RT_OK;
 }
 
-// A device buffer of at least `bytes`, reallocated (after the streams drain) when smaller.
-int grow_buffer(rt_ctx* ctx, void** p, size_t* cap, size_t bytes) {
-    if (*p && *cap >= bytes) return RT_OK;
-    RT_HIP(ctx, join_aux(ctx));
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (*p) RT_HIP(ctx, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t alloc = bytes < 256 ? 256 : bytes;
-    hipError_t e = hipMalloc(p, alloc);
-    if (e != hipSuccess) return fail(ctx, RT_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    *cap = alloc;
-    return RT_OK;
-}
-
 int collect_timing(rt_ctx* ctx) {
     if (ctx->clock_pending.empty()) return RT_OK;
     RT_HIP(ctx, join_aux(ctx));
@@ -785,6 +794,32 @@ int collect_timing(rt_ctx* ctx) {
     // here, off the launch path, instead of by a memset ahead of every timed launch
     RT_HIP(ctx, hipMemsetAsync(ctx->d_clock, 0, c.size() * 8, ctx->stream));
     ctx->primary_dirty = true;  // an auxiliary-stream batch waits for it
+    return RT_OK;
+}
+
+// The auxiliary stream follows the primary stream: what S runs next waits for everything issued
+// on the primary stream so far (nothing to do when S is the primary stream).
+hipError_t follow_primary(rt_ctx* ctx, hipStream_t S) {
+    if (S == ctx->stream) return hipSuccess;
+    const hipError_t e = hipEventRecord(ctx->ev_primary, ctx->stream);
+    return e != hipSuccess ? e : hipStreamWaitEvent(S, ctx->ev_primary, 0);
+}
+
+// ka.launch_clock: the timing slot of a launch on stream S, null unless timing is on
+// (rt_set_timing, which also allocates the ring ahead of the launches).
+int claim_clock_slot(rt_ctx* ctx, hipStream_t S, KernelArgs& ka) {
+    ka.launch_clock = nullptr;
+    if (!ctx->timing) return RT_OK;
+    int rc;
+    if (ctx->clock_pending.size() >= kClockSlots && (rc = collect_timing(ctx))) return rc;
+    if (!ctx->d_clock) {
+        if ((rc = dev_alloc(ctx, &ctx->d_clock, kClockWords * (size_t)kClockSlots))) return rc;
+        RT_HIP(ctx, follow_primary(ctx, S));  // the zeroed slots must be in place before an aux launch
+    }
+    const uint32_t slot = ctx->clock_next;
+    ctx->clock_next = (ctx->clock_next + 1) % kClockSlots;
+    ka.launch_clock = ctx->d_clock + kClockWords * (size_t)slot;  // zero: dev_alloc / collect_timing
+    ctx->clock_pending.push_back(slot);
     return RT_OK;
 }
 
@@ -1346,18 +1381,12 @@ static int scene_accel_args(rt_ctx* ctx, KernelArgs& ka, SceneLaunch& sl) {
     const bool global_walk = sl.tris && sl.mode <= 1 && ka.tri_accel && ka.tri_nodes != 0;
     const bool octants = global_walk && ctx->tri_octants_built;
     const bool qnodes = global_walk && ctx->use_qnodes;
+    int rc;
     if (octants || qnodes) {
         const uint32_t n_out = octants ? 8u * ka.tri_nodes : ka.tri_nodes;
-        if (qnodes && ctx->qnodes_cap < n_out) {
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_qnodes) RT_HIP(ctx, hipFree(ctx->d_tri_qnodes));
-            ctx->d_tri_qnodes = nullptr;
-            ctx->qnodes_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qnodes), (size_t)n_out * sizeof(uint4)));
-            ctx->qnodes_cap = n_out;
-            ctx->qnodes_dirty = true;
-        }
+        if (qnodes && (rc = grow_buffer(ctx, "quantized triangle nodes", &ctx->d_tri_qnodes, &ctx->qnodes_cap,
+                                        (size_t)n_out * sizeof(uint4), &ctx->qnodes_dirty)))
+            return rc;
         if (!ctx->d_tri_qgrid) RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_qgrid), 2 * sizeof(float4)));
         if (ctx->qnodes_dirty || ctx->derived_octants != octants || ctx->derived_qnodes != qnodes) {
             // after the accelerator's upload or refit (primary stream)
@@ -1388,17 +1417,9 @@ static int scene_accel_args(rt_ctx* ctx, KernelArgs& ka, SceneLaunch& sl) {
     ka.tri_prune = ka.tri_prune_mode == 2u ? kTriPruneRho : 0.0f;
     ka.tri_leafcert = nullptr;
     if (ka.tri_prune_mode == 1u && ka.tri_prim_count != 0 && sl.mode <= 1) {  // (mode 2 culls by box alone)
-        const size_t bytes = (size_t)ka.tri_prim_count * sizeof(TriLeafCert);
-        if (ctx->tri_lcert_cap < bytes) {  // (re)allocate: nothing may still read them
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_lcert) RT_HIP(ctx, hipFree(ctx->d_tri_lcert));
-            ctx->d_tri_lcert = nullptr;
-            ctx->tri_lcert_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_lcert), bytes));
-            ctx->tri_lcert_cap = bytes;
-            ctx->cones_dirty = true;
-        }
+        if ((rc = grow_buffer(ctx, "leaf certificates", &ctx->d_tri_lcert, &ctx->tri_lcert_cap,
+                              (size_t)ka.tri_prim_count * sizeof(TriLeafCert), &ctx->cones_dirty)))
+            return rc;
         if (ctx->cones_dirty) {
             RT_HIP(ctx, rt_launch_tri_leafcert(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_sub, ctx->d_tri,
                                                ctx->n_tri_dev, ctx->d_tri_lcert, ctx->stream));
@@ -1412,17 +1433,9 @@ static int scene_accel_args(rt_ctx* ctx, KernelArgs& ka, SceneLaunch& sl) {
     sl.coop = sl.tris && sl.mode <= 1 && ka.tri_accel && ka.tri_nodes != 0 && ka.tri_prim_count != 0 &&
                       ctx->use_coop_leaves;
     if (sl.coop) {
-        const size_t bytes = (size_t)ka.tri_prim_count * kLeafTriWords * sizeof(uint4);
-        if (ctx->tri_ltris_cap < bytes) {  // (re)allocate: nothing may still read them
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_tri_ltris) RT_HIP(ctx, hipFree(ctx->d_tri_ltris));
-            ctx->d_tri_ltris = nullptr;
-            ctx->tri_ltris_cap = 0;
-            RT_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_tri_ltris), bytes));
-            ctx->tri_ltris_cap = bytes;
-            ctx->ltris_dirty = true;
-        }
+        if ((rc = grow_buffer(ctx, "leaf triangle blocks", &ctx->d_tri_ltris, &ctx->tri_ltris_cap,
+                              (size_t)ka.tri_prim_count * kLeafTriWords * sizeof(uint4), &ctx->ltris_dirty)))
+            return rc;
         if (ctx->ltris_dirty) {
             RT_HIP(ctx, rt_launch_tri_leaftris(ctx->d_tri_prims, ka.tri_prim_count, ctx->d_tri, ctx->n_tri_dev,
                                                ctx->d_tri_ltris, ctx->stream));
@@ -1454,16 +1467,26 @@ static bool rt_path_frame_par_instance(bool frame_par_batch, uint32_t accumulate
     return enabled && frame_par_batch && accumulate == 1u && bounces >= 1u;
 }
 
-// One launch rendering `frames` frames starting at Params.accumulation_index.
-static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
-    const rt_params& p = ctx->params;
-    {
-        int rc = refresh_sphere_slots(ctx, p.sphere_count, p.object_count == 0);
-        if (rc) return rc;
-        rc = refresh_tri_accel(ctx, p.object_count);
-        if (rc) return rc;
-    }
-    KernelArgs ka{};
+// ---- a batch launch, stage by stage (dispatch_batch) --------------------------------------------
+
+// What the stages hand to each other.
+struct BatchLaunch {
+    uint32_t bounces = 0, frames = 0;
+    uint64_t owned_px = 0;
+    bool frame_par = false;    // a frame-parallel batch: (frame, tile) units, lights resolved afterwards
+    bool fp_instance = false;  // the path kernel runs as its frame-parallel instance
+    SceneLaunch sl;
+    const rt_ctx::OccEntry* occ = nullptr;  // the path launch's workgroup size and residency
+    size_t lds_bytes = 0;      // the path launch's dynamic LDS
+    uint32_t blocks = 0;       // its workgroups
+    bool sched = false;        // it claims tiles in cost order
+    int si = 0;                // the stream it runs on: 0 the primary, 1 the auxiliary one
+    hipStream_t S = nullptr;
+    bool primary = false;      // the pre-pass runs ahead of it
+};
+
+// The arguments every frame launch starts from.
+static void batch_base_args(rt_ctx* ctx, const BatchLaunch& b, KernelArgs& ka) {
     ka.camera_rays = ctx->d_rays;
     ka.accum = ctx->d_accum;
     ka.output = ctx->d_out;
@@ -1471,193 +1494,186 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     ka.diag = ctx->d_counter + 1;
     ka.queue_stripes = ctx->queue_stripes;  // (queue counters: per stream, set at launch)
     scene_base_args(ctx, ka);
-    ka.bounces = bounces;
+    ka.bounces = b.bounces;
     ka.tiles_x = ctx->tiles_x;
     ka.owned_tiles = ctx->owned_tiles;
     ka.rank = ctx->rank;
     ka.world_size = ctx->world;
     ka.drain_threshold = ctx->drain_threshold;
     ka.drain_min_steps = ctx->drain_min_steps;
-    ka.frames = frames;
-    // Frame-parallel batch: one queue unit per (frame, tile), lights resolved in order
-    // by rt_resolve_frames_kernel (accumulating renders; non-accumulating frames are
-    // all the same frame and keep the per-lane sequence).
-    const uint64_t owned_px = (uint64_t)ctx->owned_tiles * 64u;
-    const bool frame_par = frames > 1 && p.accumulate == 1u && ctx->frame_parallel &&
-                           (uint64_t)frames * p.compute_per_frame <= kMaxParallelLights && p.compute_per_frame > 0;
+    ka.frames = b.frames;
+}
+
+// Batch plan. Frame-parallel batch: one queue unit per (frame, tile), lights resolved in order
+// by rt_resolve_frames_kernel (accumulating renders; non-accumulating frames are
+// all the same frame and keep the per-lane sequence).
+static int plan_batch(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
+    const rt_params& p = ctx->params;
+    b.owned_px = (uint64_t)ctx->owned_tiles * 64u;
+    b.frame_par = b.frames > 1 && p.accumulate == 1u && ctx->frame_parallel &&
+                  (uint64_t)b.frames * p.compute_per_frame <= kMaxParallelLights && p.compute_per_frame > 0;
     ka.frame_light = nullptr;
     ka.queue_units = ctx->owned_tiles;
-    if (frame_par) {
-        const size_t need = (size_t)owned_px * frames * p.compute_per_frame;
-        if (need > ctx->frame_light_cap) {
+    if (b.frame_par) {
+        const size_t need = (size_t)b.owned_px * b.frames * p.compute_per_frame;  // float4 entries
+        if (need * sizeof(float4) > ctx->frame_light_cap) {
             // sized for the configured batch too, so a short first batch (a warmup)
             // does not leave a reallocation for a later, timed launch; two buffers,
             // one per batch parity (overlapped batches), within the batch budget
             const size_t want = std::max<size_t>(
                 need, std::min<size_t>(ctx->batch_budget / (2 * sizeof(float4)),
-                                       (size_t)owned_px * std::min<uint64_t>((uint64_t)ctx->frame_batch *
-                                                                                 p.compute_per_frame,
-                                                                             kMaxParallelLights)));
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (float4*& b : ctx->d_frame_light) {
-                if (b) RT_HIP(ctx, hipFree(b));
-                b = nullptr;
-            }
-            ctx->frame_light_cap = 0;
-            for (float4*& b : ctx->d_frame_light) {
-                const hipError_t ea = hipMalloc(reinterpret_cast<void**>(&b), want * sizeof(float4));
-                if (ea != hipSuccess) return fail(ctx, RT_E_NOMEM, std::string("frame lights: ") + hipGetErrorString(ea));
-            }
-            ctx->frame_light_cap = want;
+                                       (size_t)b.owned_px * std::min<uint64_t>((uint64_t)ctx->frame_batch *
+                                                                                   p.compute_per_frame,
+                                                                               kMaxParallelLights)));
+            const int rc = grow_buffer(ctx, "frame lights", ctx->d_frame_light, &ctx->frame_light_cap,
+                                       want * sizeof(float4), nullptr, 2);
+            if (rc) return rc;
         }
-        ka.queue_units = ctx->owned_tiles * frames;
+        ka.queue_units = ctx->owned_tiles * b.frames;
         ka.unit_tile_major = ctx->unit_tile_major ? 1u : 0u;
-        ka.light_plane = (uint32_t)owned_px;
+        ka.light_plane = (uint32_t)b.owned_px;
     }
-    const bool fp_instance = rt_path_frame_par_instance(frame_par, p.accumulate, bounces, ctx->frame_par_instance);
+    b.fp_instance = rt_path_frame_par_instance(b.frame_par, p.accumulate, b.bounces, ctx->frame_par_instance);
+    return RT_OK;
+}
 
-    SceneLaunch sl;
-    scene_carve(ctx, ka, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
-    const bool tris = sl.tris;
-    const int mode = sl.mode;
-    if (ctx->brute) {
-        // the reference's sweeps as a wavefront (rt_brute_wf_kernel): the mode-1 scene image,
-        // then the sub-object tiles (mode 1) or the hit lists (mode 2: the records through the
-        // scalar cache; a scene without triangles has no records to stream and sweeps its
-        // spheres in the LDS-tiled kernel); every pass (frame, sample) in order, one launch per
-        // bounce level
-        scene_carve_layouts(ctx, ka, 1, kLdsSceneBudget, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
-        ka.lds_srgb_offset = (uint32_t)(sl.mode1_bytes - kLdsTailBytes);
-        ka.lds_stack_offset = (uint32_t)al16(sl.mode1_bytes);
-        const uint32_t samples = ka.accumulate == 1u ? ka.compute_per_frame : 1u;
-        const uint64_t passes = (uint64_t)frames * samples;
-        const bool scalar_stream = tris && ctx->brute == 2;
-        const size_t lds = ka.lds_stack_offset + rt_brute_wf_tile_bytes(scalar_stream);
-        int dev = 0, max_optin = 0;
-        RT_HIP(ctx, hipGetDevice(&dev));
-        RT_HIP(ctx, hipDeviceGetAttribute(&max_optin, hipDeviceAttributeSharedMemPerBlockOptin, dev));
-        if (lds > (size_t)max_optin - 256)
-            return fail(ctx, RT_E_CAPACITY, "brute-force mode: spheres, materials and objects must fit in LDS");
-        ka.sphere_octant_stride = 0;
-        ka.sphere_boxes_ordered = 0;
-        ka.stream_bytes = ctx->d_stream;
-        ka.l2_stream_bytes = ctx->d_stream + 1;
-        ka.frame_light = nullptr;
-        RT_HIP(ctx, join_aux(ctx));
-        ka.launch_clock = nullptr;
-        if (ctx->timing) {
-            if (ctx->clock_pending.size() >= kClockSlots) {
-                const int rc = collect_timing(ctx);
-                if (rc) return rc;
-            }
-            if (!ctx->d_clock) {
-                const int rc = dev_alloc(ctx, &ctx->d_clock, kClockWords * (size_t)kClockSlots);
-                if (rc) return rc;
-            }
-            const uint32_t slot = ctx->clock_next;
-            ctx->clock_next = (ctx->clock_next + 1) % kClockSlots;
-            ka.launch_clock = ctx->d_clock + kClockWords * (size_t)slot;  // zero: dev_alloc / collect_timing
-            ctx->clock_pending.push_back(slot);
+// Brute-force launch: the reference's sweeps as a wavefront (rt_brute_wf_kernel): the mode-1 scene
+// image, then the sub-object tiles (mode 1) or the hit lists (mode 2: the records through the
+// scalar cache; a scene without triangles has no records to stream and sweeps its
+// spheres in the LDS-tiled kernel); every pass (frame, sample) in order, one launch per
+// bounce level
+static int launch_brute(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
+    SceneLaunch& sl = b.sl;
+    scene_carve_layouts(ctx, ka, 1, kLdsSceneBudget, ctx->force_global_scene ? 0 : ctx->max_lds_mode, sl);
+    ka.lds_srgb_offset = (uint32_t)(sl.mode1_bytes - kLdsTailBytes);
+    ka.lds_stack_offset = (uint32_t)al16(sl.mode1_bytes);
+    const uint32_t samples = ka.accumulate == 1u ? ka.compute_per_frame : 1u;
+    const uint64_t passes = (uint64_t)b.frames * samples;
+    const bool scalar_stream = sl.tris && ctx->brute == 2;
+    const size_t lds = ka.lds_stack_offset + rt_brute_wf_tile_bytes(scalar_stream);
+    int dev = 0, max_optin = 0;
+    RT_HIP(ctx, hipGetDevice(&dev));
+    RT_HIP(ctx, hipDeviceGetAttribute(&max_optin, hipDeviceAttributeSharedMemPerBlockOptin, dev));
+    if (lds > (size_t)max_optin - 256)
+        return fail(ctx, RT_E_CAPACITY, "brute-force mode: spheres, materials and objects must fit in LDS");
+    ka.sphere_octant_stride = 0;
+    ka.sphere_boxes_ordered = 0;
+    ka.stream_bytes = ctx->d_stream;
+    ka.l2_stream_bytes = ctx->d_stream + 1;
+    ka.frame_light = nullptr;
+    RT_HIP(ctx, join_aux(ctx));
+    int rc = claim_clock_slot(ctx, ctx->stream, ka);
+    if (rc) return rc;
+    const size_t n_slots = (size_t)ctx->owned_tiles * 64u;
+    // per pass one counter per bounce level: the entries of each level's queue
+    ka.brute_levels = std::max(1u, b.bounces) + 1u;
+    const size_t n_counts = (size_t)passes * ka.brute_levels;
+    if ((rc = grow_buffer(ctx, "brute-force paths", &ctx->d_brute_paths, &ctx->brute_paths_cap,
+                          4 * n_slots * sizeof(float4))) ||
+        (rc = grow_buffer(ctx, "brute-force queue", &ctx->d_brute_queue, &ctx->brute_queue_cap,
+                          2 * n_slots * sizeof(uint32_t))) ||
+        (rc = grow_buffer(ctx, "brute-force counters", &ctx->d_brute_counts, &ctx->brute_counts_cap,
+                          n_counts * sizeof(uint32_t))))
+        return rc;
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_brute_counts, 0, n_counts * sizeof(uint32_t), ctx->stream));
+    ka.brute_paths = ctx->d_brute_paths;
+    ka.brute_queue = ctx->d_brute_queue;
+    ka.brute_counts = ctx->d_brute_counts;
+    // workgroups per launch: enough for every chunk of queue entries, at most 16 per CU
+    const uint32_t chunks = (uint32_t)((n_slots + rt_brute_wf_chunk() - 1u) / rt_brute_wf_chunk());
+    const uint32_t blocks = std::min<uint32_t>(chunks, 16u * (uint32_t)std::max<int>(1, (int)ctx->n_cu));
+    for (uint64_t pass = 0; pass < passes; ++pass)
+        for (uint32_t level = 0; level < std::max(1u, b.bounces); ++level) {
+            ka.brute_pass = (uint32_t)pass;
+            ka.brute_level = level;
+            RT_HIP(ctx, rt_launch_brute_wf(ka, sl.tris, scalar_stream, lds, blocks, ctx->stream));
         }
-        const size_t n_slots = (size_t)ctx->owned_tiles * 64u;
-        // per pass one counter per bounce level: the entries of each level's queue
-        ka.brute_levels = std::max(1u, bounces) + 1u;
-        const size_t n_counts = (size_t)passes * ka.brute_levels;
-        int rc;
-        if ((rc = grow_buffer(ctx, reinterpret_cast<void**>(&ctx->d_brute_paths), &ctx->brute_paths_cap,
-                              4 * n_slots * sizeof(float4))) ||
-            (rc = grow_buffer(ctx, reinterpret_cast<void**>(&ctx->d_brute_queue), &ctx->brute_queue_cap,
-                              2 * n_slots * sizeof(uint32_t))) ||
-            (rc = grow_buffer(ctx, reinterpret_cast<void**>(&ctx->d_brute_counts), &ctx->brute_counts_cap,
-                              n_counts * sizeof(uint32_t))))
-            return rc;
-        RT_HIP(ctx, hipMemsetAsync(ctx->d_brute_counts, 0, n_counts * sizeof(uint32_t), ctx->stream));
-        ka.brute_paths = ctx->d_brute_paths;
-        ka.brute_queue = ctx->d_brute_queue;
-        ka.brute_counts = ctx->d_brute_counts;
-        // workgroups per launch: enough for every chunk of queue entries, at most 16 per CU
-        const uint32_t chunks = (uint32_t)((n_slots + rt_brute_wf_chunk() - 1u) / rt_brute_wf_chunk());
-        const uint32_t blocks = std::min<uint32_t>(chunks, 16u * (uint32_t)std::max<int>(1, (int)ctx->n_cu));
-        for (uint64_t pass = 0; pass < passes; ++pass)
-            for (uint32_t level = 0; level < std::max(1u, bounces); ++level) {
-                ka.brute_pass = (uint32_t)pass;
-                ka.brute_level = level;
-                RT_HIP(ctx, rt_launch_brute_wf(ka, tris, scalar_stream, lds, blocks, ctx->stream));
-            }
-        ctx->last_blocks = blocks;
-        ctx->last_passes = RT_PASS_BRUTE | (scalar_stream ? RT_PASS_BRUTE_STREAM : 0u);
-        ctx->last_lds = (uint32_t)lds;
-        ctx->occ_threads = 256;
-        ctx->primary_dirty = true;
-        return RT_OK;
-    }
-    {
-        const int rc = scene_accel_args(ctx, ka, sl);
-        if (rc) return rc;
-    }
-    const bool coop = sl.coop;
-    const size_t mode1_bytes = sl.mode1_bytes, mode2_bytes = sl.mode2_bytes;
-    size_t lds_bytes = sl.lds_bytes;
+    ctx->last_blocks = blocks;
+    ctx->last_passes = RT_PASS_BRUTE | (scalar_stream ? RT_PASS_BRUTE_STREAM : 0u);
+    ctx->last_lds = (uint32_t)lds;
+    ctx->last_threads = 256;  // (last_mode: the last path launch's, as rt_launch_config has always reported)
+    ctx->primary_dirty = true;
+    return RT_OK;
+}
+
+// Path occupancy. Persistent grid: as many workgroups as can be resident (never more than
+// one wave per tile); waves then pull tiles from the queue.
+static int path_occupancy(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
+    const SceneLaunch& sl = b.sl;
     // per-thread LDS after the scene image: the cooperative leaf batch's per-wave scratch
-    const size_t lane_pt = coop ? (size_t)kLeafBatchWaveBytes / 64u : 0u;
-    // Persistent grid: as many workgroups as can be resident (never more than
-    // one wave per tile); waves then pull tiles from the queue.
+    const size_t lane_pt = sl.coop ? (size_t)kLeafBatchWaveBytes / 64u : 0u;
     // The environment line (rt_kernel_args.h): the decoded texels of a rows- or columns-uniform
     // environment map, staged after the scene image's tail by the instances that stage the scene.
     size_t line_bytes = 0;
-    if (mode >= 1) {
+    if (sl.mode >= 1) {
         const uint32_t n = env_line_texels(ka.env_uniform, ka.env_w, ka.env_h);
         if (n != 0 && n <= kEnvLineMax) line_bytes = (size_t)n * sizeof(float4);
     }
-    rt_ctx::OccEntry& oc = ctx->occ_cache[fp_instance ? 1 : 0];
-    if (oc.blocks_per_cu == 0 || oc.lds_bytes != lds_bytes || oc.mode != mode || oc.tris != tris ||
-        oc.stack_pt != lane_pt || oc.force_threads != ctx->force_threads || oc.waves_cap != ctx->waves_cap ||
-        oc.line_bytes != line_bytes) {
+    const rt_ctx::OccKey key{sl.lds_bytes, lane_pt, line_bytes, sl.mode, sl.tris ? 1u : 0u, ctx->force_threads,
+                             ctx->waves_cap};
+    rt_ctx::OccEntry& oc = ctx->occ_cache[b.fp_instance ? 1 : 0];
+    if (oc.blocks_per_cu == 0 || !same_key(oc.key, key)) {
         int per_cu = 0;
         uint32_t threads = 0;
-        hipError_t oe = rt_pathtrace_pick_config(mode, tris, fp_instance, lds_bytes, lane_pt, ctx->force_threads,
-                                                 ctx->waves_cap, &threads, &per_cu);
+        hipError_t oe = rt_pathtrace_pick_config(sl.mode, sl.tris, b.fp_instance, sl.lds_bytes, lane_pt,
+                                                 ctx->force_threads, ctx->waves_cap, &threads, &per_cu);
         if (oe != hipSuccess) return hip_fail(ctx, "rt_pathtrace_pick_config (occupancy query)", oe);
         // the line is staged only where the launch keeps its workgroup size and its workgroups per CU with it
         oc.env_line = false;
         if (line_bytes != 0) {
             int per_cu_line = 0;
             uint32_t threads_line = 0;
-            oe = rt_pathtrace_pick_config(mode, tris, fp_instance, lds_bytes + line_bytes, lane_pt, ctx->force_threads,
-                                          ctx->waves_cap, &threads_line, &per_cu_line);
+            oe = rt_pathtrace_pick_config(sl.mode, sl.tris, b.fp_instance, sl.lds_bytes + line_bytes, lane_pt,
+                                          ctx->force_threads, ctx->waves_cap, &threads_line, &per_cu_line);
             if (oe != hipSuccess) (void)hipGetLastError();  // no configuration holds it: the global path
             oc.env_line = oe == hipSuccess && threads_line == threads && per_cu_line == per_cu;
         }
-        oc.line_bytes = line_bytes;
+        oc.key = key;
         oc.blocks_per_cu = per_cu;
         oc.threads = threads;
-        oc.lds_bytes = lds_bytes;
-        oc.mode = mode;
-        oc.tris = tris;
-        oc.stack_pt = lane_pt;
-        oc.force_threads = ctx->force_threads;
-        oc.waves_cap = ctx->waves_cap;
     }
+    b.occ = &oc;
     // this launch's configuration (rt_launch_config reports it)
-    ctx->occ_blocks_per_cu = oc.blocks_per_cu;
-    ctx->occ_threads = oc.threads;
-    ctx->occ_lds_bytes = lds_bytes;
-    ctx->occ_mode = mode;
-    ctx->occ_tris = tris;
-    ctx->occ_stack_pt = lane_pt;
+    ctx->last_threads = oc.threads;
+    ctx->last_mode = sl.mode;
+    b.lds_bytes = sl.lds_bytes;
     if (oc.env_line) {  // right after the tail (a multiple of 16 bytes, as the image before it)
         ka.env_uniform |= kEnvLineStaged;
-        lds_bytes += line_bytes;
+        b.lds_bytes += line_bytes;
     }
     // the leaf batch scratch after the scene image, its tail and the environment line
-    ka.lds_leafbatch_offset = (uint32_t)al16(lds_bytes);
-    if (coop) lds_bytes = ka.lds_leafbatch_offset + (size_t)ctx->occ_threads * lane_pt;
-    const uint32_t waves_per_block = ctx->occ_threads / 64;
-    const uint64_t resident = (uint64_t)ctx->occ_blocks_per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
+    ka.lds_leafbatch_offset = (uint32_t)al16(b.lds_bytes);
+    if (sl.coop) b.lds_bytes = ka.lds_leafbatch_offset + (size_t)oc.threads * lane_pt;
+    const uint32_t waves_per_block = oc.threads / 64;
+    const uint64_t resident = (uint64_t)oc.blocks_per_cu * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 1);
     const uint64_t wanted = ((uint64_t)ka.queue_units + waves_per_block - 1) / waves_per_block;
-    const uint32_t blocks = (uint32_t)(wanted < resident ? wanted : resident);
-    if (blocks == 0) return RT_OK;
+    b.blocks = (uint32_t)(wanted < resident ? wanted : resident);
+    return RT_OK;
+}
+
+// Stream and queue selection.
+// Overlapped batches: frame-parallel batches alternate between
+// the primary and the auxiliary stream. Batch i's path kernel depends on no
+// other batch (it writes its own light buffer, i % 2), so it starts on the CUs
+// that batch i-1's drain frees; only its resolve waits for batch i-1's resolve
+// (the accumulation order). Everything else stays on the primary stream.
+static int select_stream(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
+    b.si = (b.frame_par && ctx->batch_overlap) ? (int)(ctx->batches & 1u) : 0;
+    b.S = b.si ? ctx->aux_stream : ctx->stream;
+    if (!b.frame_par) RT_HIP(ctx, join_aux(ctx));  // a plain launch follows every earlier batch
+    if (b.si && ctx->primary_dirty) {  // primary-stream work (uploads, resets) the batch must follow
+        RT_HIP(ctx, follow_primary(ctx, b.S));
+        ctx->primary_dirty = false;
+    }
+    const uint32_t parity = ctx->queue_parity[b.si];
+    ka.queue = ctx->d_queue + (size_t)(2 * b.si + parity) * kQueueStripesMax * kQueueStride;
+    ka.queue_next = ctx->d_queue + (size_t)(2 * b.si + (parity ^ 1u)) * kQueueStripesMax * kQueueStride;
+    if (b.frame_par) ka.frame_light = ctx->d_frame_light[ctx->batches & 1u];
+    return RT_OK;
+}
+
+// Schedule state.
+static int schedule_state(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
     // Cost-ordered schedule, when each wave takes several tiles per launch (with
     // about one tile per wave the claim order cannot shorten the drain, and the
     // sort would sit on a short launch's critical path).
@@ -1665,134 +1681,121 @@ static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
     // (and overlapped) the cost order's recording and sort cost more than they save,
     // and index order keeps neighbouring tiles together (C2 -5.2%, C3 -2.7% per frame
     // measured, profiles/archive/r02_knobs); RT_BATCH_SCHEDULE=1 sorts them too (A/B switch).
-    const bool sched = ctx->tile_schedule && (!frame_par || ctx->batch_schedule) &&
-                       (uint64_t)ka.queue_units >= kSchedMinTilesPerWave * blocks * waves_per_block;
-    // Overlapped batches: frame-parallel batches alternate between
-    // the primary and the auxiliary stream. Batch i's path kernel depends on no
-    // other batch (it writes its own light buffer, i % 2), so it starts on the CUs
-    // that batch i-1's drain frees; only its resolve waits for batch i-1's resolve
-    // (the accumulation order). Everything else stays on the primary stream.
-    const int si = (frame_par && ctx->batch_overlap) ? (int)(ctx->batches & 1u) : 0;
-    hipStream_t S = si ? ctx->aux_stream : ctx->stream;
-    if (!frame_par) RT_HIP(ctx, join_aux(ctx));  // a plain launch follows every earlier batch
-    if (si && ctx->primary_dirty) {  // primary-stream work (uploads, resets) the batch must follow
-        RT_HIP(ctx, hipEventRecord(ctx->ev_primary, ctx->stream));
-        RT_HIP(ctx, hipStreamWaitEvent(S, ctx->ev_primary, 0));
-        ctx->primary_dirty = false;
+    const uint32_t waves_per_block = b.occ->threads / 64;
+    b.sched = ctx->tile_schedule && (!b.frame_par || ctx->batch_schedule) &&
+              (uint64_t)ka.queue_units >= kSchedMinTilesPerWave * b.blocks * waves_per_block;
+    if (!b.sched) return RT_OK;
+    const size_t n = ctx->owned_tiles;
+    uint32_t*& state = ctx->d_tile_sched[b.si];
+    if (!state) {
+        int rc = dev_alloc(ctx, &state, 4 * n + 2);
+        if (rc) return rc;
+        RT_HIP(ctx, hipMemsetAsync(state, 0, (4 * n + 2) * 4, ctx->stream));
+        ctx->primary_dirty = true;
+        RT_HIP(ctx, follow_primary(ctx, b.S));
+        ctx->sched_launches[b.si] = 0;
     }
-    ka.queue = ctx->d_queue + (size_t)(2 * si + ctx->queue_parity[si]) * kQueueStripesMax * kQueueStride;
-    ka.queue_next = ctx->d_queue + (size_t)(2 * si + (ctx->queue_parity[si] ^ 1u)) * kQueueStripesMax * kQueueStride;
-    if (frame_par) ka.frame_light = ctx->d_frame_light[ctx->batches & 1u];
-    if (sched) {
-        const size_t n = ctx->owned_tiles;
-        uint32_t*& state = ctx->d_tile_sched[si];
-        if (!state) {
-            int rc = dev_alloc(ctx, &state, 4 * n + 2);
-            if (rc) return rc;
-            RT_HIP(ctx, hipMemsetAsync(state, 0, (4 * n + 2) * 4, ctx->stream));
-            ctx->primary_dirty = true;
-            if (si) {
-                RT_HIP(ctx, hipEventRecord(ctx->ev_primary, ctx->stream));
-                RT_HIP(ctx, hipStreamWaitEvent(S, ctx->ev_primary, 0));
-            }
-            ctx->sched_launches[si] = 0;
-        }
-        ka.sched = state;
-        // orders[parity] was written by this stream's previous launch
-        ka.sched_bits = (uint32_t)(ctx->sched_launches[si] & 1u);
-        ka.tile_cost = ka.sched + ka.sched_bits * (size_t)n;
-        ka.tile_order = ctx->sched_launches[si] ? ka.sched + (2u + ka.sched_bits) * (size_t)n : nullptr;
-    }
+    ka.sched = state;
+    // orders[parity] was written by this stream's previous launch
+    ka.sched_bits = (uint32_t)(ctx->sched_launches[b.si] & 1u);
+    ka.tile_cost = ka.sched + ka.sched_bits * (size_t)n;
+    ka.tile_order = ctx->sched_launches[b.si] ? ka.sched + (2u + ka.sched_bits) * (size_t)n : nullptr;
+    return RT_OK;
+}
 
-    ka.launch_clock = nullptr;
-    if (ctx->timing) {
-        if (ctx->clock_pending.size() >= kClockSlots) {
-            const int rc = collect_timing(ctx);
-            if (rc) return rc;
-        }
-        if (!ctx->d_clock) {
-            const int rc = dev_alloc(ctx, &ctx->d_clock, kClockWords * (size_t)kClockSlots);
-            if (rc) return rc;
-            if (si) {  // the zeroed slots must be in place before an aux launch
-                RT_HIP(ctx, hipEventRecord(ctx->ev_primary, ctx->stream));
-                RT_HIP(ctx, hipStreamWaitEvent(S, ctx->ev_primary, 0));
-            }
-        }
-        const uint32_t slot = ctx->clock_next;
-        ctx->clock_next = (ctx->clock_next + 1) % kClockSlots;
-        ka.launch_clock = ctx->d_clock + kClockWords * (size_t)slot;  // zero: dev_alloc / collect_timing
-        ctx->clock_pending.push_back(slot);
-    }
-    // Coherent primary rays: the first segment of every (frame, sample, pixel) of the launch
-    // traced by rt_primary_kernel as 8x8 packets, stream-ordered before the path kernel
-    // (scene image in LDS, binary triangle accelerator). By default only where the triangle
-    // accelerator stays in global memory (mode 1 with triangles, C5: wall -12%); with the
-    // accelerator in LDS (C3, C4) or no triangles (C2) the pass costs more wall time than it
-    // takes off the path kernel (+13%, +13%, +23%: profiles/r03_i/ab_primary.jsonl)
-    // (within the batch budget: a batch too large for it traces its first segments in the path kernel)
-    const size_t primary_need =
-        (size_t)owned_px * frames * std::max<uint32_t>(1u, p.accumulate == 1u ? p.compute_per_frame : 1u);
-    const bool primary = bounces > 0 && mode >= 1 && tris && ka.compute_per_frame > 0 &&
-                         (ctx->primary_pass == 1 || (ctx->primary_pass == -1 && mode == 1)) &&
-                         2 * primary_need * sizeof(uint4) <= ctx->batch_budget;
+// Primary pre-pass.
+// Coherent primary rays: the first segment of every (frame, sample, pixel) of the launch
+// traced by rt_primary_kernel as 8x8 packets, stream-ordered before the path kernel
+// (scene image in LDS, binary triangle accelerator). By default only where the triangle
+// accelerator stays in global memory (mode 1 with triangles, C5: wall -12%); with the
+// accelerator in LDS (C3, C4) or no triangles (C2) the pass costs more wall time than it
+// takes off the path kernel (+13%, +13%, +23%: profiles/r03_i/ab_primary.jsonl)
+// (within the batch budget: a batch too large for it traces its first segments in the path kernel)
+static int primary_prepass(rt_ctx* ctx, BatchLaunch& b, KernelArgs& ka) {
+    const rt_params& p = ctx->params;
+    const SceneLaunch& sl = b.sl;
+    const size_t need =  // records
+        (size_t)b.owned_px * b.frames * std::max<uint32_t>(1u, p.accumulate == 1u ? p.compute_per_frame : 1u);
+    b.primary = b.bounces > 0 && sl.mode >= 1 && sl.tris && ka.compute_per_frame > 0 &&
+                (ctx->primary_pass == 1 || (ctx->primary_pass == -1 && sl.mode == 1)) &&
+                2 * need * sizeof(uint4) <= ctx->batch_budget;
     ka.primary = nullptr;
-    if (primary) {
-        const int pi = (int)(ctx->batches & 1u);
-        const size_t need = primary_need;
-        if (need > ctx->primary_cap) {
-            RT_HIP(ctx, join_aux(ctx));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const size_t want = std::max<size_t>(
-                need, std::min<size_t>(ctx->batch_budget / (2 * sizeof(uint4)), (size_t)owned_px * ctx->frame_batch));
-            for (uint4*& b : ctx->d_primary) {
-                if (b) RT_HIP(ctx, hipFree(b));
-                b = nullptr;
-            }
-            ctx->primary_cap = 0;
-            for (uint4*& b : ctx->d_primary) {
-                const hipError_t ea = hipMalloc(reinterpret_cast<void**>(&b), want * 16);
-                if (ea != hipSuccess) return fail(ctx, RT_E_NOMEM, std::string("primary records: ") + hipGetErrorString(ea));
-            }
-            ctx->primary_cap = want;
-        }
-        KernelArgs pka = ka;
-        pka.primary = ctx->d_primary[pi];
-        pka.queue_units = ctx->owned_tiles * frames;  // one unit per (frame, tile)
-        pka.primary_tile_major = ctx->primary_tile_major ? 1u : 0u;
-        const size_t image = mode == 2 ? mode2_bytes : mode1_bytes;
-        // (the 64-VGPR variant is built at 256 threads only)
-        const uint32_t min_waves = (mode == 2 || ctx->primary_threads != 256u) ? 0u : ctx->primary_min_waves;
-        RT_HIP(ctx, rt_launch_primary(pka, mode, tris, image, mode == 2 ? 1024u : ctx->primary_threads, min_waves, S));
-        ka.primary = pka.primary;
+    if (!b.primary) return RT_OK;
+    if (need * sizeof(uint4) > ctx->primary_cap) {
+        const size_t want = std::max<size_t>(
+            need, std::min<size_t>(ctx->batch_budget / (2 * sizeof(uint4)), (size_t)b.owned_px * ctx->frame_batch));
+        const int rc = grow_buffer(ctx, "primary records", ctx->d_primary, &ctx->primary_cap, want * sizeof(uint4),
+                                   nullptr, 2);
+        if (rc) return rc;
     }
-    hipError_t e = rt_launch_pathtrace(ka, mode, tris, fp_instance, ctx->occ_threads, lds_bytes, blocks, S);
-    ctx->last_blocks = blocks;
-    ctx->last_passes = RT_PASS_PATH | (primary ? RT_PASS_PRIMARY : 0u) | (frame_par ? RT_PASS_RESOLVE : 0u) |
-                       (fp_instance ? RT_PASS_PATH_FRAME_PAR : 0u);
-    ctx->last_lds = (uint32_t)lds_bytes;
+    KernelArgs pka = ka;
+    pka.primary = ctx->d_primary[ctx->batches & 1u];
+    pka.queue_units = ctx->owned_tiles * b.frames;  // one unit per (frame, tile)
+    pka.primary_tile_major = ctx->primary_tile_major ? 1u : 0u;
+    const size_t image = sl.mode == 2 ? sl.mode2_bytes : sl.mode1_bytes;
+    // (the 64-VGPR variant is built at 256 threads only)
+    const uint32_t min_waves = (sl.mode == 2 || ctx->primary_threads != 256u) ? 0u : ctx->primary_min_waves;
+    RT_HIP(ctx, rt_launch_primary(pka, sl.mode, sl.tris, image, sl.mode == 2 ? 1024u : ctx->primary_threads, min_waves,
+                                  b.S));
+    ka.primary = pka.primary;
+    return RT_OK;
+}
+
+// The path kernel, the batch's resolve, and the end-of-launch bookkeeping.
+static int launch_path_and_resolve(rt_ctx* ctx, const BatchLaunch& b, const KernelArgs& ka) {
+    const rt_params& p = ctx->params;
+    hipError_t e = rt_launch_pathtrace(ka, b.sl.mode, b.sl.tris, b.fp_instance, b.occ->threads, b.lds_bytes, b.blocks,
+                                       b.S);
+    ctx->last_blocks = b.blocks;
+    ctx->last_passes = RT_PASS_PATH | (b.primary ? RT_PASS_PRIMARY : 0u) | (b.frame_par ? RT_PASS_RESOLVE : 0u) |
+                       (b.fp_instance ? RT_PASS_PATH_FRAME_PAR : 0u);
+    ctx->last_lds = (uint32_t)b.lds_bytes;
     if (e != hipSuccess) return hip_fail(ctx, "rt_pathtrace_kernel launch", e);
-    if (frame_par) {
+    if (b.frame_par) {
         // the accumulation is summed in frame order: after the previous batch's resolve
-        if (ctx->batches > 0) RT_HIP(ctx, hipStreamWaitEvent(S, ctx->ev_resolved[(ctx->batches - 1) & 1u], 0));
+        if (ctx->batches > 0) RT_HIP(ctx, hipStreamWaitEvent(b.S, ctx->ev_resolved[(ctx->batches - 1) & 1u], 0));
         e = rt_launch_resolve(ctx->d_accum, ctx->d_out, ka.frame_light, ctx->width, ctx->height, ctx->tiles_x,
                               ctx->owned_tiles, ctx->rank, ctx->world, p.accumulation_index, p.compute_per_frame,
-                              frames, ka.launch_clock ? ka.launch_clock + 2 : nullptr, S);
+                              b.frames, ka.launch_clock ? ka.launch_clock + 2 : nullptr, b.S);
         if (e != hipSuccess) return hip_fail(ctx, "rt_resolve_frames_kernel launch", e);
-        RT_HIP(ctx, hipEventRecord(ctx->ev_resolved[ctx->batches & 1u], S));
+        RT_HIP(ctx, hipEventRecord(ctx->ev_resolved[ctx->batches & 1u], b.S));
         ctx->batches += 1;
     }
     // every tile is claimed once and every wave makes one final failing claim
-    ctx->queue_parity[si] ^= 1u;  // this launch zeroes the other half for the stream's next one
-    if (si) {
-        RT_HIP(ctx, hipEventRecord(ctx->ev_aux_done, S));
+    ctx->queue_parity[b.si] ^= 1u;  // this launch zeroes the other half for the stream's next one
+    if (b.si) {
+        RT_HIP(ctx, hipEventRecord(ctx->ev_aux_done, b.S));
         ctx->aux_outstanding = true;
     }
     // A plain launch (not frame-parallel) reads and writes the accumulation and
     // the output on the primary stream; a later overlapped batch on the auxiliary
     // stream must follow it (its resolve writes both), not just the previous batch.
-    if (!frame_par) ctx->primary_dirty = true;
-    if (sched) ++ctx->sched_launches[si];
+    if (!b.frame_par) ctx->primary_dirty = true;
+    if (b.sched) ++ctx->sched_launches[b.si];
     return RT_OK;
+}
+
+// One launch rendering `frames` frames starting at Params.accumulation_index.
+static int dispatch_batch(rt_ctx* ctx, uint32_t bounces, uint32_t frames) {
+    const rt_params& p = ctx->params;
+    int rc;
+    if ((rc = refresh_sphere_slots(ctx, p.sphere_count, p.object_count == 0)) ||
+        (rc = refresh_tri_accel(ctx, p.object_count)))
+        return rc;
+    KernelArgs ka{};
+    BatchLaunch b;
+    b.bounces = bounces;
+    b.frames = frames;
+    batch_base_args(ctx, b, ka);
+    if ((rc = plan_batch(ctx, b, ka))) return rc;
+    scene_carve(ctx, ka, ctx->force_global_scene ? 0 : ctx->max_lds_mode, b.sl);
+    if (ctx->brute) return launch_brute(ctx, b, ka);
+    if ((rc = scene_accel_args(ctx, ka, b.sl)) || (rc = path_occupancy(ctx, b, ka))) return rc;
+    if (b.blocks == 0) return RT_OK;
+    if ((rc = select_stream(ctx, b, ka)) || (rc = schedule_state(ctx, b, ka)) ||
+        (rc = claim_clock_slot(ctx, b.S, ka)) || (rc = primary_prepass(ctx, b, ka)))
+        return rc;
+    return launch_path_and_resolve(ctx, b, ka);
 }
 
 // Queueing a frame is host bookkeeping only: the device is selected (a HIP call)
@@ -1959,15 +1962,12 @@ static int query_scene(rt_ctx* ctx, uint64_t count, int kind, QueryLaunch& q) {
         const uint32_t threads = kQueryKernels[kind].threads(sl.mode, sl.tris);
         ka.lds_leafbatch_offset = (uint32_t)al16(sl.lds_bytes);
         q.lds_bytes = sl.coop ? ka.lds_leafbatch_offset + (size_t)(threads / 64u) * kLeafBatchWaveBytes : sl.lds_bytes;
-        if (ctx->q_occ_blocks == 0 || ctx->q_occ_mode != sl.mode || ctx->q_occ_kind != kind ||
-            ctx->q_occ_tris != sl.tris || ctx->q_occ_lds != q.lds_bytes) {
+        const rt_ctx::QueryOccKey key{sl.mode, kind, sl.tris ? 1u : 0u, (uint32_t)q.lds_bytes};
+        if (ctx->q_occ_blocks == 0 || !same_key(ctx->q_occ_key, key)) {
             int n = 0;
             const hipError_t e = kQueryKernels[kind].occupancy(sl.mode, sl.tris, q.lds_bytes, &n);
             if (e != hipSuccess) (void)hipGetLastError();
-            ctx->q_occ_mode = sl.mode;
-            ctx->q_occ_kind = kind;
-            ctx->q_occ_tris = sl.tris;
-            ctx->q_occ_lds = q.lds_bytes;
+            ctx->q_occ_key = key;
             ctx->q_occ_blocks = e == hipSuccess ? n : 0;
         }
         if (ctx->q_occ_blocks > 0) break;
@@ -2001,7 +2001,7 @@ static int run_query(rt_ctx* ctx, const void* rays, void* hits, uint64_t count, 
 // pinned.
 static int query_buffers(rt_ctx* ctx, size_t n) {
     if (ctx->query_buf_rays < n) {
-        const int rc = grow_buffer(ctx, &ctx->d_query_buf, &ctx->query_buf_bytes, n * (sizeof(rt_query_ray) + sizeof(rt_hit)));
+        const int rc = grow_buffer(ctx, "query scratch", &ctx->d_query_buf, &ctx->query_buf_bytes, n * (sizeof(rt_query_ray) + sizeof(rt_hit)));
         if (rc) return rc;
         ctx->query_buf_rays = n;
     }
@@ -2160,7 +2160,7 @@ static int build_features(rt_ctx* ctx) {
         if (!plane && (rc = dev_alloc(ctx, &plane, ctx->n_pixels))) return rc;
     if (!ctx->d_feat_ids && (rc = dev_alloc(ctx, &ctx->d_feat_ids, ctx->n_pixels))) return rc;
     const uint64_t band = std::min<uint64_t>(ctx->n_pixels, ctx->feature_band);
-    if ((rc = grow_buffer(ctx, &ctx->d_feat_scratch, &ctx->feat_scratch_bytes,
+    if ((rc = grow_buffer(ctx, "feature scratch", &ctx->d_feat_scratch, &ctx->feat_scratch_bytes,
                           band * (sizeof(rt_query_ray) + sizeof(rt_hit)))))
         return rc;
     unsigned char* d_rays = static_cast<unsigned char*>(ctx->d_feat_scratch);
@@ -2367,7 +2367,7 @@ static int denoise_temporal(rt_ctx* ctx, const std::string& who, const rt_tempor
         // objects first; copied through the pinned staging area, so the caller's arrays are free on return
         const size_t ob = (size_t)mt->object_count * sizeof(rt_motion), sb = (size_t)mt->sphere_count * sizeof(rt_motion);
         if (ob + sb) {
-            if ((rc = grow_buffer(ctx, &ctx->d_motion, &ctx->motion_bytes, ob + sb))) return rc;
+            if ((rc = grow_buffer(ctx, "motion records", &ctx->d_motion, &ctx->motion_bytes, ob + sb))) return rc;
             void* p;
             if ((rc = staging(ctx, ob + sb, &p))) return rc;
             if (ob) std::memcpy(p, mt->objects, ob);
@@ -2682,7 +2682,7 @@ static int run_striped(rt_ctx* ctx, const QueryLaunch& q, const void* points, vo
                        uint32_t samples, const char* what, Launch launch) {
     const uint32_t stripes = std::min<uint32_t>(samples, 64u);
     const uint64_t chunk = std::min<uint64_t>(count, ctx->gather_chunk);
-    const int rc = grow_buffer(ctx, &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u);
+    const int rc = grow_buffer(ctx, "gather partials", &ctx->d_gather_partials, &ctx->gather_partials_bytes, (size_t)chunk * 1024u);
     if (rc) return rc;
     for (uint64_t done = 0; done < count;) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, count - done);
@@ -2806,7 +2806,7 @@ static int run_probe_sh(rt_ctx* ctx, const void* probes, void* sh, uint64_t coun
     // mostly fill and drain (four items per resident lane), and the next launch's workgroups take
     // the CUs the draining one gives up. Not where that would take the scratch beyond its cap.
     const bool overlap = count > chunk && 2u * bytes <= kMaxProbeScratchBytes;
-    if ((rc = grow_buffer(ctx, &ctx->d_probe_lights, &ctx->probe_lights_bytes, overlap ? 2u * bytes : bytes))) return rc;
+    if ((rc = grow_buffer(ctx, "probe lights", &ctx->d_probe_lights, &ctx->probe_lights_bytes, overlap ? 2u * bytes : bytes))) return rc;
     if (overlap) {
         if (!ctx->d_probe_next && (rc = dev_alloc(ctx, &ctx->d_probe_next, 2))) return rc;
         RT_HIP(ctx, hipEventRecord(ctx->ev_primary, ctx->stream));  // the probes are there, the scratch is free
@@ -3260,12 +3260,8 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         if (v != 0 && v != 256 && v != 512 && v != 1024)
             return fail(ctx, RT_E_INVALID, "rt_set_tuning: block_threads must be 0, 256, 512 or 1024");
         ctx->force_threads = (uint32_t)v;
-        ctx->occ_blocks_per_cu = 0;
     } else if (k == "waves_per_cu") {
-        if ((rc = range(0, 32)) == RT_OK) {
-            ctx->waves_cap = (uint32_t)v;
-            ctx->occ_blocks_per_cu = 0;
-        }
+        if ((rc = range(0, 32)) == RT_OK) ctx->waves_cap = (uint32_t)v;
     } else if (k == "tri_bvh") {
         if ((rc = flag(ctx->use_tri_bvh)) == RT_OK) ctx->tri_dirty = true;
     } else if (k == "tri_octants") {
@@ -3563,10 +3559,10 @@ int rt_launch_config(rt_ctx* ctx, uint32_t* threads, uint32_t* blocks, uint32_t*
                      uint32_t* scene_in_lds) {
     RT_ENTER(ctx);  // the last launch: queued frames launched first
     if (!threads || !blocks || !lds_bytes || !scene_in_lds) return RT_E_INVALID;
-    *threads = ctx->occ_threads;
+    *threads = ctx->last_threads;
     *blocks = ctx->last_blocks;
     *lds_bytes = ctx->last_lds;
-    *scene_in_lds = ctx->occ_mode < 0 ? 0u : (uint32_t)ctx->occ_mode;
+    *scene_in_lds = ctx->last_mode < 0 ? 0u : (uint32_t)ctx->last_mode;
     return RT_OK;
 }
 

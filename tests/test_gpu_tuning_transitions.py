@@ -404,6 +404,42 @@ def test_growth_across_a_change(gpu, oracle_lib):
         assert mismatches == 0 and total > 0, (mismatches, valid, total)
 
 
+def test_batch_buffers_grow_between_overlapped_batches(gpu, oracle_lib):
+    """G with frame_batch 2: the first batch sizes the frame lights and the primary records for
+    batches of 2. Batches of 2, 2, 8 and 2 frames: the batch of 8 needs more of both, so both
+    pairs are reallocated while the batch before it ran on the other stream, and the batch after
+    it runs in the larger buffers. Every batch equals the oracle's running result."""
+    ref = reference("G")
+    with Renderer(ref.scene, camera_rays=ref.rays, frame_batch=2) as r:
+        run = Run(r, ref, 2)
+        for i, frames in enumerate((2, 2, 8, 2)):
+            now = run.step(f"G: batch {i} of {frames} frames", frames=frames)
+            if frames == 8:  # a frame-parallel batch with the pre-pass: the two buffers that grew
+                assert now.mask & N.RT_PASS_PRIMARY and now.mask & N.RT_PASS_RESOLVE, now
+        assert run.k == 14
+
+
+def test_launch_timing_across_overlapped_batches(gpu, oracle_lib):
+    """S in batches of 3: one untimed batch (the primary stream), then timing on and four more,
+    the first of them on the auxiliary stream behind the primary stream's zeroing of the clock
+    slots. One path launch and one resolve per frame-parallel batch: exactly 4 timed spans of
+    each, with positive totals (no bound on the times), and the 15 frames equal the oracle's."""
+    ref = reference("S")
+    with Renderer(ref.scene, camera_rays=ref.rays, frame_batch=3) as r:
+        run = Run(r, ref, 3)
+        run.step("S: the untimed batch")
+        r.set_timing(True)
+        for i in range(4):
+            now = run.step(f"S: timed batch {i}")
+            assert now.mask & N.RT_PASS_RESOLVE, now
+        r.synchronize()
+        ms, n = r.dispatch_time_total()
+        assert n == 4 and ms > 0.0, (ms, n)
+        ms, n = r.resolve_time_total()
+        assert n == 4 and ms > 0.0, (ms, n)
+        assert run.k == 15
+
+
 # ---------------------------------------------------------------------------- 4. the schedule key
 def test_tile_schedule_key_discards_the_recorded_schedule(gpu, oracle_lib):
     """The size and pattern of test_cluster_scene_claims_in_sorted_order (512x256, "waves_per_cu" 1,
