@@ -60,7 +60,9 @@ extern "C" {
  * 12, additive: motion records for the temporal denoiser (rt_denoise_temporal_motion, rt_motion,
  * rt_motion_from_transforms, rt_read_feature_ids, rt_feature_ids_device);
  * 12, additive: lens queries (rt_lens, rt_lens_device, rt_lens_rays, rt_lens_rays_device,
- * rt_lens_camera). */
+ * rt_lens_camera);
+ * 12, additive: hit-list queries (rt_trace_hits, rt_trace_hits_device, rt_pick_hits,
+ * RT_HITS_MAX). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -430,6 +432,70 @@ _Static_assert(sizeof(rt_occlusion_ray) == 32, "rt_occlusion_ray is 32 bytes");
  * RT_E_INVALID. */
 RT_API int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count);
 RT_API int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_device, uint64_t count);
+
+/* ---- hit-list queries (ABI 12, additive: hit-list queries) -----------------
+ *
+ * "What are the things along this ray, in order?" for arbitrary rays: the max_hits nearest
+ * primitives of each ray, each as the rt_hit record of a closest-hit query. Click-through
+ * picking, shadow rays attenuated by the glass they cross, thickness and crossing counts,
+ * "is the camera inside an object". The input record is rt_occlusion_ray, so one buffer serves
+ * rt_trace_rays, rt_occluded and rt_trace_hits; ray i's entries are
+ * hits[i * max_hits .. i * max_hits + max_hits).
+ *
+ * THE HIT-LIST CONTRACT. For the ray (o, d, t_max) and a list length max_hits in 1..RT_HITS_MAX:
+ *  1. Bound. bound = min(t_max, 3.4028235e38f). A t_max that is <= 0 or NaN gives no candidates.
+ *  2. Sphere candidates. Sphere i is a candidate when the test of check_spheres
+ *     (compute_shader.wgsl:355-404) on it alone accepts it: not disc < 0, and
+ *     t = (-b - sqrt(disc)) / (2a) with t > 0; and t < bound. One candidate per sphere, the near
+ *     root, as in the reference.
+ *  3. Triangle candidates. A visit (object oi, sub-object slot i, triangle slot j) of the sweep of
+ *     check_triangles (:422-517) is a candidate when it is behind the ray_in_bounds tests of its
+ *     object and of its sub-object, with the reference's index clamps; none of the reference's
+ *     rejections dist < 0, v < 0, u < 0, w < 0 holds (dist >= 0 and u, v, w >= 0); and its
+ *     distance is not NaN and is < bound. Its sweep position seq is its position in the sweep's
+ *     order over all (object, sub-object slot, triangle slot) triples, boxes disregarded.
+ *  4. NaN distances. A candidate with a NaN distance is never listed: the any-hit rule, and the
+ *     one difference from the closest-hit record.
+ *  5. Order. Ascending t. At equal t triangles come before spheres, triangles ascend by seq and
+ *     spheres ascend by index as uploaded: the order in which trace_ray (:342-353) and the two
+ *     sweeps would prefer them.
+ *  6. Result. n = min(number of candidates, max_hits). Entries 0..n-1 are the first n candidates
+ *     in that order, each the rt_hit record rt_trace_rays builds for that primitive at that t:
+ *     position, facing normal, u and v whatever the texture size, material, front_face, kind,
+ *     index, sub_object, triangle. Entries n..max_hits-1 are the miss record: all zero,
+ *     t = 3.4028235e38f. counts[i] = n. Every entry of every ray is written and nothing else is.
+ *
+ * Consequences:
+ *  1. With t_max = +inf, entry 0 is the record of rt_trace_rays bit for bit, for every ray whose
+ *     closest-hit search meets no NaN distance.
+ *  2. counts[i] > 0 exactly when rt_occluded answers 1 for the same record, for any t_max.
+ *  3. Lists nest: the list for max_hits = K is the first K entries of the list for any K' > K.
+ *  4. counts saturates at max_hits. A caller that must know whether a list is complete asks for
+ *     one entry more than it uses.
+ *  5. The exactness domain, scene visibility and side effects are those of rt_trace_rays. There
+ *     are no side effects: queued frames stay queued, and nothing a render observes changes. The
+ *     result does not depend on the brute-force mode, on any rt_set_tuning key ("query_lds_mode"
+ *     included) or on triangle pruning modes 0 and 1. It works on rank contexts. The search
+ *     terminates on any input: the walks' skip links only advance.
+ *
+ * rt_trace_hits: host pointers, synchronous; `counts` may be NULL. Staged through the pinned
+ * buffer of rt_trace_rays in chunks of max(1, "query_chunk" / max_hits) rays.
+ * rt_trace_hits_device: device pointers on the context's device, rays and hits 16-byte aligned,
+ * counts (may be NULL) 4-byte aligned; stream-ordered on rt_stream(ctx), no host copy,
+ * asynchronous. While the call runs, the hits buffer also holds the lists being built.
+ * rt_pick_hits: the list of pixel (x, y)'s un-jittered camera ray as rt_pick defines it, with
+ * t_max = +inf; *n receives the count. Synchronous.
+ * RT_E_INVALID: max_hits == 0 or > RT_HITS_MAX, whatever count is; NULL rays or hits with
+ * count > 0 (rt_pick_hits: NULL hits or n); pointers that are not device memory of the context's
+ * device, or misaligned (the device form); x or y outside the framebuffer. count == 0 returns
+ * RT_OK and launches nothing. */
+#define RT_HITS_MAX 16u
+RT_API int rt_trace_hits(rt_ctx* ctx, const rt_occlusion_ray* rays, rt_hit* hits /* count * max_hits */,
+                         uint32_t* counts /* count; may be NULL */, uint64_t count, uint32_t max_hits);
+RT_API int rt_trace_hits_device(rt_ctx* ctx, const void* rays_device, void* hits_device,
+                                void* counts_device /* may be NULL */, uint64_t count, uint32_t max_hits);
+RT_API int rt_pick_hits(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hits /* max_hits */, uint32_t* n,
+                        uint32_t max_hits);
 
 /* ---- radiance queries (ABI 12, additive: radiance queries) -----------------
  *

@@ -204,6 +204,9 @@ SIGNATURES = {
     "rt_pick": (ctypes.c_int, [_P, _U32, _U32, _P]),
     "rt_occluded": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_occluded_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_trace_hits": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, _U32]),
+    "rt_trace_hits_device": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, _U32]),
+    "rt_pick_hits": (ctypes.c_int, [_P, _U32, _U32, _P, ctypes.POINTER(_U32), _U32]),
     "rt_radiance": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_radiance_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_gather": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
@@ -318,6 +321,7 @@ RT_PASS_PATH, RT_PASS_PRIMARY, RT_PASS_RESOLVE, RT_PASS_BRUTE, RT_PASS_BRUTE_STR
 RT_PASS_PATH_FRAME_PAR = 64  # with RT_PASS_PATH: the path kernel's frame-parallel instance ran
 RT_GROUP_COPY_TRANSPORT = 1  # rt_create_multi_ex flags
 RT_LENS_PERSPECTIVE, RT_LENS_ORTHOGRAPHIC, RT_LENS_EQUIRECT = 0, 1, 2  # rt_lens_camera.kind
+RT_HITS_MAX = 16  # the longest list of rt_trace_hits
 RT_GATHER_IMAGE = 0
 RT_GATHER_ACCUMULATION = 1
 RT_DISPLAY_ACCUMULATION, RT_DISPLAY_DENOISED, RT_DISPLAY_PLANE = 0, 1, 2  # rt_display_params.source

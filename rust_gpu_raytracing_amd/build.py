@@ -20,7 +20,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 INCLUDE = ROOT / "include"
 OUT = PKG / "librt_pathtrace.so"
-SOURCES = [CSRC / "pathtrace.hip", CSRC / "query.hip", CSRC / "occlusion.hip", CSRC / "ambient.hip", CSRC / "radiance.hip", CSRC / "denoise.hip",
+SOURCES = [CSRC / "pathtrace.hip", CSRC / "query.hip", CSRC / "occlusion.hip", CSRC / "hits.hip", CSRC / "ambient.hip", CSRC / "radiance.hip", CSRC / "denoise.hip",
            CSRC / "display.hip", CSRC / "scene_edit.hip", CSRC / "rt_abi.cpp", CSRC / "sphere_bvh.cpp", CSRC / "scene_build.cpp", CSRC / "rt_multi.cpp"]
 HEADERS = [CSRC / "rt_bvh_slab.h", CSRC / "rt_device_math.h", CSRC / "rt_kernel_args.h", CSRC / "sphere_bvh.h",
            CSRC / "rt_scene_math.h", CSRC / "tri_qnode.h", CSRC / "tri_cone.h", CSRC / "rt_path_common.h",

@@ -1911,7 +1911,7 @@ static int query_enter(rt_ctx* ctx) {
 // rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
 // its gather instance (points x samples) or its probe instance (probes x samples), or
 // rt_ambient_kernel (ambient.hip; points x samples), or the radiance kernel's lens instance
-// (pixels x samples).
+// (pixels x samples), or rt_hits_kernel (hits.hip).
 enum QueryKind {
     kQueryClosest = 0,
     kQueryAnyHit = 1,
@@ -1919,20 +1919,22 @@ enum QueryKind {
     kQueryGather = 3,
     kQueryProbe = 4,
     kQueryAmbient = 5,
-    kQueryLens = 6
+    kQueryLens = 6,
+    kQueryHits = 7
 };
 
 // Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
 static const struct {
     uint32_t (*threads)(int mode, bool tris);
     hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-} kQueryKernels[7] = {{rt_query_threads, rt_query_occupancy},
+} kQueryKernels[8] = {{rt_query_threads, rt_query_occupancy},
                       {rt_occlusion_threads, rt_occlusion_occupancy},
                       {rt_radiance_threads, rt_radiance_occupancy},
                       {rt_radiance_threads, rt_gather_occupancy},
                       {rt_radiance_threads, rt_probe_occupancy},
                       {rt_ambient_threads, rt_ambient_occupancy},
-                      {rt_radiance_threads, rt_lens_occupancy}};
+                      {rt_radiance_threads, rt_lens_occupancy},
+                      {rt_hits_threads, rt_hits_occupancy}};
 
 struct QueryLaunch {
     KernelArgs ka{};
@@ -2602,6 +2604,101 @@ int rt_occluded_device(rt_ctx* ctx, const void* rays_device, void* occluded_devi
 int rt_occluded(rt_ctx* ctx, const rt_occlusion_ray* rays, uint8_t* occluded, uint64_t count) {
     return staged_query(ctx, kOccluded, rays, occluded, count, 0, nullptr,
                         [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_query(ctx, in, out, n, true); });
+}
+
+// ---- hit-list queries (hits.hip) ---------------------------------------------------------------
+//
+// The K nearest hits of each ray, with the scene visibility and the absence of side effects of the
+// calls above: `count` rt_occlusion_ray at device pointer `rays` into count x max_hits rt_hit at
+// `hits` and, unless null, one count per ray at `counts`. `pick`: the rays are rt_pick's (no t_max).
+static int run_hits(rt_ctx* ctx, const void* rays, void* hits, void* counts, uint64_t count, uint32_t max_hits,
+                    bool pick = false) {
+    if (count == 0) return RT_OK;
+    QueryLaunch q;
+    const int rc = query_scene(ctx, count, kQueryHits, q);
+    if (rc) return rc;
+    // every chunk from the counter, as the closest-hit kernel takes them
+    const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident, 0u, rtq::kWalkChunkMax);
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    const hipError_t e = rt_launch_hits(q.ka, q.sl.mode, q.sl.tris, q.lds_bytes, s, rays, hits, counts, count, max_hits,
+                                        pick, ctx->d_query_next, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_hits_kernel launch", e);
+    return RT_OK;
+}
+
+// The check on max_hits, which comes first: an entry point refuses it whatever `count` is.
+static int check_max_hits(rt_ctx* ctx, const char* entry, uint32_t max_hits) {
+    if (max_hits == 0 || max_hits > RT_HITS_MAX)
+        return fail(ctx, RT_E_INVALID, std::string(entry) + ": max_hits must be in [1, " + std::to_string(RT_HITS_MAX) + "]");
+    return RT_OK;
+}
+
+int rt_trace_hits_device(rt_ctx* ctx, const void* rays_device, void* hits_device, void* counts_device, uint64_t count,
+                         uint32_t max_hits) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_max_hits(ctx, "rt_trace_hits_device", max_hits);
+    if (rc || count == 0) return rc;
+    rc = check_device_ptrs(ctx, "rt_trace_hits_device",
+                           {{rays_device, "rays", 16, false}, {hits_device, "hits", 16, false}, {counts_device, "counts", 4, true}});
+    if (rc || (rc = query_enter(ctx))) return rc;
+    return run_hits(ctx, rays_device, hits_device, counts_device, count, max_hits);
+}
+
+// Staged through the buffers of rt_trace_rays in chunks of max(1, query_chunk / max_hits) rays: a
+// chunk's rays at the base, then its records, then its counts.
+int rt_trace_hits(rt_ctx* ctx, const rt_occlusion_ray* rays, rt_hit* hits, uint32_t* counts, uint64_t count,
+                  uint32_t max_hits) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_max_hits(ctx, "rt_trace_hits", max_hits);
+    if (rc || count == 0) return rc;
+    if (!rays || !hits) return fail(ctx, RT_E_INVALID, "rt_trace_hits: rays or hits is NULL");
+    if ((rc = query_enter(ctx))) return rc;
+    const size_t chunk = (size_t)std::min<uint64_t>(count, std::max<uint32_t>(1u, ctx->query_chunk / max_hits));
+    const size_t ray_bytes = sizeof(rt_occlusion_ray), list_bytes = (size_t)max_hits * sizeof(rt_hit);
+    // (a scratch "ray" is 96 bytes: chunk x max_hits of them hold the records, chunk more the rays and counts)
+    if ((rc = query_buffers(ctx, chunk * max_hits + chunk))) return rc;
+    unsigned char* d_in = static_cast<unsigned char*>(ctx->d_query_buf);
+    unsigned char* h_in = static_cast<unsigned char*>(ctx->query_pinned);
+    const size_t hits_at = chunk * ray_bytes, counts_at = hits_at + chunk * list_bytes;
+    for (uint64_t done = 0; done < count;) {
+        const size_t n = (size_t)std::min<uint64_t>(chunk, count - done);
+        std::memcpy(h_in, rays + done, n * ray_bytes);
+        RT_HIP(ctx, hipMemcpyAsync(d_in, h_in, n * ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = run_hits(ctx, d_in, d_in + hits_at, d_in + counts_at, n, max_hits))) return rc;
+        RT_HIP(ctx, hipMemcpyAsync(h_in + hits_at, d_in + hits_at, n * list_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(h_in + counts_at, d_in + counts_at, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::memcpy(hits + done * max_hits, h_in + hits_at, n * list_bytes);
+        if (counts) std::memcpy(counts + done, h_in + counts_at, n * sizeof(uint32_t));
+        done += n;
+    }
+    return RT_OK;
+}
+
+int rt_pick_hits(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hits, uint32_t* n, uint32_t max_hits) {
+    RT_ENTER_NOFLUSH(ctx);
+    int rc = check_max_hits(ctx, "rt_pick_hits", max_hits);
+    if (rc) return rc;
+    if (!hits || !n) return fail(ctx, RT_E_INVALID, "rt_pick_hits: hits or n is NULL");
+    if (x >= ctx->width || y >= ctx->height)
+        return fail(ctx, RT_E_INVALID, "rt_pick_hits: pixel outside the framebuffer");
+    if ((rc = query_enter(ctx)) || (rc = query_buffers(ctx, (size_t)max_hits + 1u))) return rc;
+    unsigned char* d_ray = static_cast<unsigned char*>(ctx->d_query_buf);
+    const size_t hits_at = sizeof(rt_query_ray), list_bytes = (size_t)max_hits * sizeof(rt_hit);
+    {
+        // rt_pick's ray (its record carries no t_max: the kernel takes +inf)
+        KernelArgs ka{};
+        scene_base_args(ctx, ka);
+        ka.camera_rays = ctx->d_rays;
+        RT_HIP(ctx, rt_launch_pick_ray(ka, x, y, d_ray, ctx->stream));
+    }
+    if ((rc = run_hits(ctx, d_ray, d_ray + hits_at, d_ray + hits_at + list_bytes, 1, max_hits, true))) return rc;
+    unsigned char* h_out = static_cast<unsigned char*>(ctx->query_pinned);
+    RT_HIP(ctx, hipMemcpyAsync(h_out, d_ray + hits_at, list_bytes + sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(hits, h_out, list_bytes);
+    std::memcpy(n, h_out + list_bytes, sizeof(uint32_t));
+    return RT_OK;
 }
 
 // ---- radiance queries (radiance.hip) -----------------------------------------------------------

@@ -75,6 +75,12 @@ hipError_t rt_occlusion_occupancy(int mode, bool tris, size_t lds_bytes, int* bl
 hipError_t rt_launch_occlusion(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                                const void* rays, void* occluded, uint64_t count, unsigned long long* counter,
                                hipStream_t stream);
+// hits.hip: `counts` may be null; `pick`: the rays carry no t_max (rt_launch_pick_ray's record)
+uint32_t rt_hits_threads(int mode, bool tris);
+hipError_t rt_hits_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_hits(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
+                          const void* rays, void* hits, void* counts, uint64_t count, uint32_t max_hits, bool pick,
+                          unsigned long long* counter, hipStream_t stream);
 uint32_t rt_radiance_threads(int mode, bool tris);
 hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
 hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);

@@ -372,6 +372,27 @@ class Renderer:
         return hit[0]
 
     # ------------------------------------------------------------------ occlusion queries
+    @staticmethod
+    def _occlusion_rays(rays, t_max):
+        """The flat ``buffers.OCCLUSION_RAY`` array of the host forms ``occluded`` and
+        ``trace_hits`` accept."""
+        rays = np.asarray(rays)
+        if rays.dtype == B.OCCLUSION_RAY:
+            if t_max is not None:
+                raise ValueError("OCCLUSION_RAY records carry their own t_max")
+        else:
+            r = np.ascontiguousarray(rays, np.float32)
+            if r.ndim != 2 or r.shape[1] not in (6, 7) or (r.shape[1] == 7 and t_max is not None):
+                raise ValueError("rays must be (n, 7) float32, (n, 6) float32 with t_max, or an OCCLUSION_RAY array")
+            rays = np.zeros(r.shape[0], B.OCCLUSION_RAY)
+            rays["origin"] = r[:, :3]
+            rays["direction"] = r[:, 3:6]
+            if r.shape[1] == 7:
+                rays["t_max"] = r[:, 6]
+            else:
+                rays["t_max"] = Renderer._t_max_column(np.inf if t_max is None else t_max, r.shape[0])
+        return np.ascontiguousarray(rays.reshape(-1))
+
     def occluded(self, rays, t_max=None):
         """Whether anything lies on each ray before its ``t_max`` (rt_occluded): 1 iff a primitive
         is hit at a distance strictly below t_max (in units of |direction|, like ``HIT["t"]``),
@@ -387,22 +408,7 @@ class Renderer:
             if t_max is not None:
                 raise ValueError("device rays carry t_max in their last column")
             return self._device_query("rt_occluded_device", rays, 8, "rays", (), "uint8", call_empty=False)
-        rays = np.asarray(rays)
-        if rays.dtype == B.OCCLUSION_RAY:
-            if t_max is not None:
-                raise ValueError("OCCLUSION_RAY records carry their own t_max")
-        else:
-            r = np.ascontiguousarray(rays, np.float32)
-            if r.ndim != 2 or r.shape[1] not in (6, 7) or (r.shape[1] == 7 and t_max is not None):
-                raise ValueError("rays must be (n, 7) float32, (n, 6) float32 with t_max, or an OCCLUSION_RAY array")
-            rays = np.zeros(r.shape[0], B.OCCLUSION_RAY)
-            rays["origin"] = r[:, :3]
-            rays["direction"] = r[:, 3:6]
-            if r.shape[1] == 7:
-                rays["t_max"] = r[:, 6]
-            else:
-                rays["t_max"] = self._t_max_column(np.inf if t_max is None else t_max, r.shape[0])
-        rays = np.ascontiguousarray(rays.reshape(-1))
+        rays = self._occlusion_rays(rays, t_max)
         out = np.zeros(rays.shape[0], np.uint8)
         self._call("rt_occluded", N.ptr(rays), N.ptr(out), rays.shape[0])
         return out
@@ -419,6 +425,59 @@ class Renderer:
         rays["direction"] = b - a
         rays["t_max"] = 1.0
         return self.occluded(rays)
+
+    # ------------------------------------------------------------------ hit-list queries
+    def trace_hits(self, rays, t_max=None, max_hits: int = 4):
+        """The ``max_hits`` nearest hits of every ray before its ``t_max``, in order
+        (rt_trace_hits; THE HIT-LIST CONTRACT in include/rt_abi.h): every primitive the
+        reference's test accepts on its own, ascending by distance, each as the record
+        ``trace_rays`` builds for it, against the scene as it is now, without touching anything a
+        render reads.
+
+        ``rays``: what ``occluded`` accepts. Returns ``(hits, counts)``: an (n, max_hits)
+        ``buffers.HIT`` array whose entries past a ray's count are miss records, and an (n,) uint32
+        array of counts (saturating at ``max_hits``). A CUDA torch tensor of shape (n, 8) float32
+        (rt_occlusion_ray records) goes through rt_trace_hits_device instead -- no host round
+        trip, stream-ordered on the context's stream -- and returns CUDA tensors: (n, max_hits, 16)
+        int32 records and (n,) int32 counts."""
+        max_hits = int(max_hits)
+        if not isinstance(rays, np.ndarray) and hasattr(rays, "is_cuda"):
+            import torch
+
+            if t_max is not None:
+                raise ValueError("device rays carry t_max in their last column")
+            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("device rays must be a CUDA float32 tensor of shape (n, 8)")
+            if rays.device.index != self.device:
+                raise ValueError("device rays must live on the renderer's device")
+            rays = rays.contiguous()
+            n = rays.shape[0]
+            hits = torch.empty((n, max(max_hits, 0), 16), dtype=torch.int32, device=rays.device)
+            counts = torch.empty((n,), dtype=torch.int32, device=rays.device)
+            # the query runs on the context's stream: after the tensor's producers, before the
+            # caller's stream goes on (_device_query)
+            mine = torch.cuda.ExternalStream(self.stream_handle, device=rays.device)
+            cur = torch.cuda.current_stream(rays.device)
+            mine.wait_stream(cur)
+            self._call("rt_trace_hits_device", ctypes.c_void_p(rays.data_ptr() if n else None),
+                       ctypes.c_void_p(hits.data_ptr() if n and max_hits > 0 else None),
+                       ctypes.c_void_p(counts.data_ptr() if n else None), n, max_hits)
+            cur.wait_stream(mine)
+            return hits, counts
+        rays = self._occlusion_rays(rays, t_max)
+        hits = np.zeros((rays.shape[0], max(max_hits, 0)), B.HIT)
+        counts = np.zeros(rays.shape[0], np.uint32)
+        self._call("rt_trace_hits", N.ptr(rays), N.ptr(hits), N.ptr(counts), rays.shape[0], max_hits)
+        return hits, counts
+
+    def pick_hits(self, x: int, y: int, max_hits: int = 4) -> np.ndarray:
+        """The hits of pixel (x, y)'s un-jittered camera ray, nearest first (rt_pick_hits): the
+        valid records of that ray's list, at most ``max_hits`` of them."""
+        max_hits = int(max_hits)
+        hits = np.zeros(max(max_hits, 1), B.HIT)
+        n = ctypes.c_uint32()
+        self._call("rt_pick_hits", int(x), int(y), N.ptr(hits), ctypes.byref(n), max_hits)
+        return hits[:n.value]
 
     # ------------------------------------------------------------------ radiance queries
     def radiance(self, rays, streams=None, bounces: int = REFERENCE_BOUNCES, first_sample: int = 1,

@@ -1,7 +1,7 @@
 """Throughput of the ray-query kernel (rt_trace_rays_device) and its placement crossover.
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
-                                   [--reps 20] [--sweep] [--occluded] [--radiance] [--gather] [--probe] [--ambient]
+                                   [--reps 20] [--sweep] [--occluded] [--hits] [--radiance] [--gather] [--probe] [--ambient]
                                    [--lens]
                                    [--out profiles/query_bench.jsonl]
 
@@ -25,6 +25,11 @@ node); (d) shadow rays from each hit point, offset 1e-4 along the normal, toward
 direction, t_max = +inf. Device events around `reps` launches on the context's stream; the series
 alternate over --rounds rounds; median, minimum and maximum Mray/s per series. With --sweep: the
 placement crossover of the occlusion kernel, as the default sweep measures the closest-hit one's.
+--hits: the hit-list kernel (rt_trace_hits_device) against the closest-hit call on the same rays in
+the same process: the camera rays with t_max = +inf at max_hits 1, 4 and 16, next
+to rt_trace_rays_device, the yardstick. Entry 0 of every list is checked against the closest-hit
+record. Device events around `reps` launches on the context's stream; the series alternate over
+--rounds rounds; median, minimum and maximum Mray/s per series, and the mean count per ray.
 --radiance: the radiance kernel (rt_radiance_device) against the frame it reproduces, in one process
 (DESIGN.md §5.4e). The frame's own rays -- camera origin, each pixel's direction, stream = pixel
 index, samples = 1 -- are submitted as one batch; the yardstick is the same context rendering one
@@ -178,6 +183,52 @@ def occlusion_bench(r, args, q, dev, emit):
              reps=args.reps, mray_s=round(float(np.median(v)), 1), mray_s_min=round(min(v), 1),
              mray_s_max=round(max(v), 1), occluded_fraction=None if k not in fraction else round(fraction[k], 4),
              hit_fraction=round(float(hit.mean()), 4), build=r._lib.rt_build_hash().decode())
+
+
+def hits_bench(r, args, q, dev, emit):
+    """The --hits series (module docstring)."""
+    import torch
+
+    n = q.shape[0]
+    rays = q.view(B.OCCLUSION_RAY).copy()
+    rays["t_max"] = np.inf
+    rays_t = torch.from_numpy(rays.view(np.float32).reshape(-1, 8)).to(dev)
+    closest_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    counts_t = torch.empty((n,), dtype=torch.int32, device=dev)
+    lists_t = {k: torch.empty((n, k, 16), dtype=torch.int32, device=dev) for k in (1, 4, 16)}
+    torch.cuda.synchronize()  # uploaded on torch's stream, read on the context's
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+    P = ctypes.c_void_p
+
+    def launch(k):
+        if k == 0:
+            r._call("rt_trace_rays_device", P(rays_t.data_ptr()), P(closest_t.data_ptr()), n)
+        else:
+            r._call("rt_trace_hits_device", P(rays_t.data_ptr()), P(lists_t[k].data_ptr()), P(counts_t.data_ptr()), n, k)
+
+    series = {"a_closest_hit": 0, "b_hits_1": 1, "c_hits_4": 4, "d_hits_16": 16}
+    mean_count = {}
+    for name, k in series.items():  # warm-up and a check of what is timed
+        launch(k)
+        r.synchronize()
+        if k:
+            mean_count[name] = float(counts_t.sum(dtype=torch.int64).item()) / n
+            assert torch.equal(lists_t[k][:, 0], closest_t), name  # consequence 1 of the contract
+    rates = {name: [] for name in series}
+    for _ in range(args.rounds):
+        for name, k in series.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            for _ in range(args.reps):
+                launch(k)
+            t1.record(stream)
+            t1.synchronize()
+            rates[name].append(n * args.reps / (t0.elapsed_time(t1) * 1e-3) / 1e6)
+    for name, v in rates.items():
+        emit(kind="hits", series=name, max_hits=series[name] or None, rays=n, rounds=args.rounds, reps=args.reps,
+             mray_s=round(float(np.median(v)), 1), mray_s_min=round(min(v), 1), mray_s_max=round(max(v), 1),
+             ms=round(n / float(np.median(v)) / 1e3, 4),
+             mean_count=None if name not in mean_count else round(mean_count[name], 3), build=r._lib.rt_build_hash().decode())
 
 
 def radiance_bench(r, args, scene, bounces, dev, emit):
@@ -737,6 +788,7 @@ def main():
     ap.add_argument("--frames", type=int, default=32, help="frames of the render yardstick")
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
+    ap.add_argument("--hits", action="store_true", help="the hit-list kernel against the closest-hit call")
     ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
     ap.add_argument("--gather", action="store_true", help="the gather query against the same paths done by hand")
     ap.add_argument("--probe", action="store_true", help="the probe query against the same paths done by hand")
@@ -803,6 +855,8 @@ def main():
             radiance_bench(r, args, scene, bounces if args.bounces is None else args.bounces, dev, emit)
         elif args.occluded and not args.sweep:
             occlusion_bench(r, args, q, dev, emit)
+        elif args.hits:
+            hits_bench(r, args, q, dev, emit)
         elif args.sweep:
             sizes = [s for s in (64, 256, 1024, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 1048576) if s < n] + [n]
             for m in sizes:
