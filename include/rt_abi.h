@@ -353,6 +353,9 @@ _Static_assert(sizeof(rt_hit) == 64, "rt_hit is 64 bytes");
  * Exactness holds for the domain the culling bounds are derived for (DESIGN.md §5.2,
  * §5.3c): finite components, |direction| in [1e-5, 1e5], |origin| <= 1e15. Outside it the
  * record is unspecified; the search still terminates (the walks' skip links only advance).
+ * What makes tiny directions inexact is the slab test's reciprocal cap: |1/d| is held at 1e30
+ * per axis, and once it binds on more than one axis the box distances no longer follow the
+ * ray, so normalise a direction of unknown length rather than rely on the margin below 1e-5.
  *
  * rt_trace_rays: host pointers, synchronous. Rays and records are staged through pinned
  * memory in chunks of tuning "query_chunk" rays, so `count` is not limited by a scratch

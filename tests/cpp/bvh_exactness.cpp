@@ -3,6 +3,8 @@
 // order, compiled with -ffp-contract=off) must return exactly the sphere and
 // t of the reference's brute-force scan (compute_shader.wgsl:355-404).
 // usage: bvh_exactness <n_rays> <seed>   -> prints "ok <rays> <hits> <avg_tests>" or the first mismatch
+//        bvh_exactness <n_rays> <seed> dump <spheres.bin>   -> writes the scene of that seed (rt_scene_sphere records)
+//        bvh_exactness --replay <rays.f32> <spheres.bin>    -> "replay rays <n> mismatches <m> ...", exit 1 on any
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -306,6 +308,12 @@ int main(int argc, char** argv) {
     add(4, -1, 0, 1);           // exact duplicate: tie must go to the lower index
     add(4.5f, -1.2f, 0.3f, 0.7f);  // overlapping
     add(0.0f, -3.0f, 0.0f, 0.001f); // tiny
+    if (argc > 4 && strcmp(argv[3], "dump") == 0) {
+        FILE* f = fopen(argv[4], "wb");
+        if (!f || fwrite(s.data(), sizeof(rt_scene_sphere), s.size(), f) != s.size()) { perror(argv[4]); return 2; }
+        fclose(f);
+        return 0;
+    }
     SphereSlots sl;
     build_sphere_slots(s.data(), (uint32_t)s.size(), true, &sl);
     if (sl.nodes.empty()) { printf("no bvh built\n"); return 2; }

@@ -13,7 +13,11 @@ import os
 import subprocess
 from pathlib import Path
 
+import numpy as np
 import pytest
+
+from rust_gpu_raytracing_amd import buffers as B
+from tests import ray_domain as RD
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -77,3 +81,26 @@ def test_adversarial_bound_is_load_bearing(harness):
     env = dict(os.environ, LAT_SCALE="0.03")
     out = subprocess.run([str(harness), "300000", "1", "adv"], capture_output=True, text=True, env=env)
     assert out.returncode == 1 and "MISMATCH" in out.stdout
+
+
+@pytest.mark.parametrize("inv_ulp", [False, True])
+@pytest.mark.parametrize("name", ["mixed_components", "far_origins"])
+def test_ray_domain_sets(harness, tmp_path, name, inv_ulp):
+    """The harness's RTIOW-like scene (dumped, then replayed) on two in-domain sets of
+    tests/ray_domain.py: components scaled down to denormals and signed zeros with |d| from
+    1.01e-5 to 0.99e5, and origins 1e3, 1e5 and 1e7 from the spheres; with exact reciprocals and
+    with every component of 1/d one ulp off (the sphere-only kernels' v_rcp_f32). The length sweep
+    itself is test_bvh_adversarial_derived_bound's."""
+    sph = tmp_path / "spheres.bin"
+    subprocess.run([str(harness), "0", "6", "dump", str(sph)], check=True)
+    spheres = np.fromfile(sph, B.SPHERE)
+    assert spheres.shape[0] > 400
+    geo = RD.geometry(2, spheres)
+    rays = RD.ray_set(name, 70 + RD.SETS.index(name), 20000, geo)
+    rays.tofile(tmp_path / "rays.f32")
+    env = dict(os.environ, INV_ULP="1") if inv_ulp else None
+    out = subprocess.run([str(harness), "--replay", str(tmp_path / "rays.f32"), str(sph)], capture_output=True,
+                         text=True, env=env)
+    assert out.returncode == 0 and out.stdout.startswith("replay rays 20000 mismatches 0 "), out.stdout
+    accepted = float(out.stdout.splitlines()[0].split("accepted")[1])
+    assert accepted > 0.25  # (candidates accepted per ray: the set does hit spheres)

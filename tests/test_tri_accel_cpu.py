@@ -7,6 +7,8 @@ including first-wins ties (duplicate triangles), objects sharing sub-objects,
 grazing rays, and rays lying exactly in a triangle's plane (NaN distance, which
 the sweep accepts unconditionally and the kernel hands back to the sweep).
 """
+import functools
+import os
 import subprocess
 from pathlib import Path
 
@@ -15,6 +17,7 @@ import pytest
 
 from rust_gpu_raytracing_amd import buffers as B
 from rust_gpu_raytracing_amd.scene import SceneObject, build_config, load_stl_files, load_chess_assets
+from tests import ray_domain as RD
 from tests.adversarial import grazing_rays, tilted_plane_grid
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -29,10 +32,14 @@ def harness(tmp_path_factory):
     return exe
 
 
-def run(harness, tmp_path, objs, subs, tris, rays, margin=None, env=None):
+def write_inputs(tmp_path, objs, subs, tris, rays):
     for name, arr in (("o", objs), ("s", subs), ("t", tris), ("r", rays.astype(np.float32))):
         np.ascontiguousarray(arr).tofile(tmp_path / f"{name}.bin")
-    cmd = [str(harness)] + [str(tmp_path / f"{n}.bin") for n in "ostr"] + ([margin] if margin else [])
+    return [str(tmp_path / f"{n}.bin") for n in "ostr"]
+
+
+def run(harness, tmp_path, objs, subs, tris, rays, margin=None, env=None):
+    cmd = [str(harness)] + write_inputs(tmp_path, objs, subs, tris, rays) + ([margin] if margin else [])
     return subprocess.run(cmd, capture_output=True, text=True, env=env)
 
 
@@ -208,3 +215,74 @@ def test_certified_pruning_real_scenes(harness, tmp_path):
     assert int(valid) == int(total)
     box_tests = float(out.stdout.splitlines()[0].split()[3])
     assert float(skipped) > 0 and float(tests) < box_tests
+
+
+# ---------------------------------------------------------------------------- the documented ray domain
+DOMAIN_RAYS = 20000
+HEUR_COUNTED = dict(os.environ, TRI_HEUR_COUNT="1")
+
+
+@functools.lru_cache(maxsize=None)
+def domain_scene(key):
+    """(objects, sub-objects, triangles, ray_domain.Geometry) of a scene of the domain tests
+    (never modified). The harness walks triangles only; the spheres only shape the ray sets."""
+    spheres = None
+    if key == "tilted":  # coordinates that are not exactly representable
+        objs, subs, tris, _, _ = tilted_plane_grid(4, n=60)
+    else:
+        config, kw = {"c3": ("c3_chess", dict(env_size=(16, 8), texture_size=(8, 8))),
+                      "c5": ("c5_heightfield", dict(nx=40, nz=20))}[key]
+        scene, _ = build_config(config, width=16, height=16, **kw)
+        objs, subs, tris = scene.flatten()
+        spheres = scene.spheres
+    return objs, subs, tris, RD.geometry(1, spheres, objs, subs, tris)
+
+
+@pytest.mark.parametrize("name", RD.SETS)
+@pytest.mark.parametrize("key", ["c3", "c5", "tilted"])
+def test_ray_domain_edges_exact(harness, tmp_path, key, name):
+    """The four in-domain sets of tests/ray_domain.py (|d| at 1.01e-5 .. 0.99e5, components down
+    to denormals and signed zeros, origins 1e3 .. 1e7 away, origins inside boxes and within 1e-4 of
+    surfaces): every walk returns the sweep's triangle on every ray. On the tilted grid the
+    round-3 heuristic limit (pruning mode 2, documented as inexact) is counted instead, as in
+    test_adversarial_grazing_rays_certified_pruning: origins within 1e-4 of the plane are its
+    grazing regime (3 of 20,000 near_and_inside rays)."""
+    objs, subs, tris, geo = domain_scene(key)
+    rays = RD.ray_set(name, 40 + RD.SETS.index(name), DOMAIN_RAYS, geo)
+    out = run(harness, tmp_path, objs, subs, tris, rays, env=HEUR_COUNTED if key == "tilted" else None)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout
+    assert line(out, "qnodes")[0] == "1"
+    hits = int(out.stdout.splitlines()[0].split()[2])
+    assert DOMAIN_RAYS // 10 < hits < DOMAIN_RAYS  # hits and misses of the triangles
+
+
+# |d| below the domain: the decade at which the harness first reports a mismatch, per scene
+# (DESIGN.md §5.3c records the values observed)
+HEADROOM = 1e-6 * RD.D_MIN
+BELOW_DOMAIN = [1e-11, 1e-18, 1e-25] + [10.0 ** -k for k in range(26, 37)]
+
+
+@pytest.mark.parametrize("key", ["c3", "c5", "tilted"])
+def test_below_the_domain_characterisation(harness, tmp_path, key):
+    """Out of the domain (CPU only; the contract leaves such records unspecified): the aimed rays
+    of ``length_edges`` at |d| = 1e-11, 1e-18, 1e-25, 1e-26, ..., 1e-36. Every run ends, and the
+    first length at which a walk differs from the sweep (the reciprocal cap of rt_bvh_slab.h at
+    1e30 changing the ratios between axes) lies at or below 1e-6 x the domain's lower end."""
+    objs, subs, tris, geo = domain_scene(key)
+    base = RD.length_edges(60, DOMAIN_RAYS, geo.region, geo.targets)
+    first_bad = None
+    for scale in BELOW_DOMAIN:
+        rays = base.copy()
+        with np.errstate(under="ignore"):
+            rays[:, 3:] = RD.rescale(base[:, 3:], np.full(DOMAIN_RAYS, scale))
+        cmd_out = subprocess.run([str(harness)] + write_inputs(tmp_path, objs, subs, tris, rays), capture_output=True,
+                                 text=True, timeout=120,  # (a walk that does not end raises TimeoutExpired)
+                                 env=HEUR_COUNTED)  # (the exact walks: pruning mode 2's misses are not fatal)
+        assert cmd_out.returncode in (0, 1), cmd_out.stdout
+        if cmd_out.returncode == 0:
+            assert cmd_out.stdout.startswith("ok"), cmd_out.stdout
+        else:
+            assert "MISMATCH" in cmd_out.stdout, cmd_out.stdout
+            first_bad = first_bad or scale
+    print(f"below-domain first mismatch {key}: {first_bad}")
+    assert first_bad is None or first_bad <= HEADROOM, (key, first_bad)
