@@ -332,7 +332,7 @@ __device__ __forceinline__ uint32_t lds_address(const void* p) {
 //
 // kFramePar selects the frame-parallel instance ("Frame-parallel instance"): the launch is a
 // frame-parallel batch (ka.frame_light set, accumulating) with bounces >= 1, which
-// the host guarantees (rt_path_frame_par_instance, rt_abi.cpp). A finished sample
+// the host guarantees (rt_path_frame_par_instance, rt_frames.cpp). A finished sample
 // then only stores its light, so the instance holds no in-lane accumulation
 // (`pix`), no store_frame, no in-lane frame advance, no run-time test of the launch
 // mode, and no sample that ends without a trace in setup. The generic instance
@@ -960,7 +960,7 @@ __global__ void __launch_bounds__(kThreads, 1) rt_pathtrace_kernel(KernelArgs ka
 // registers: the kernel arguments of the triangle path no longer spill).
 // Each comes twice: the generic instance, which serves every launch mode, and the
 // frame-parallel instance (kFramePar), which the host selects for frame-parallel
-// batches with bounces >= 1 (rt_path_frame_par_instance, rt_abi.cpp).
+// batches with bounces >= 1 (rt_path_frame_par_instance, rt_frames.cpp).
 // (mode, threads, triangles, frame-parallel instance)
 #define RT_FOR_EACH_SHAPE(X, FP)                                                                                \
     X(0, 256, true, FP) X(0, 512, true, FP) X(0, 1024, true, FP) X(1, 256, true, FP) X(1, 512, true, FP)       \
@@ -1586,7 +1586,7 @@ hipError_t allow_big_lds(const void* fn) {
 }
 }  // namespace
 
-// frame_par: the frame-parallel instance, for a launch rt_path_frame_par_instance (rt_abi.cpp) accepts.
+// frame_par: the frame-parallel instance, for a launch rt_path_frame_par_instance (rt_frames.cpp) accepts.
 hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
                                size_t lds_bytes, uint32_t blocks, hipStream_t stream) {
     if (frame_par && (!ka.frame_light || ka.accumulate != 1u || ka.bounces == 0)) return hipErrorInvalidValue;

@@ -1,5 +1,6 @@
 // rt_launch.h — what the translation units of the library call in one another: the kernel
-// launchers and launch queries that the .hip files define for rt_abi.cpp, and rt_abi.cpp's
+// launchers and launch queries that the .hip files define for the host files (rt_abi.cpp,
+// rt_frames.cpp, rt_queries.cpp, rt_post.cpp; rt_ctx.h is what those share), and rt_abi.cpp's
 // rt_set_global_error. Every file that defines one of these includes this header, so a signature
 // that drifts is seen where it is defined, and the library is linked with --no-undefined, so one
 // that is declared and called but nowhere defined fails the build.
@@ -17,10 +18,10 @@
 #include "tri_cone.h"
 #include "tri_qnode.h"
 
-// rt_abi.cpp: the last error of a call without a context, rt_last_error(NULL)
+// rt_abi.cpp, for scene_build.cpp and rt_multi.cpp: the last error of a call without a context, rt_last_error(NULL)
 void rt_set_global_error(const std::string& msg);
 
-// pathtrace.hip
+// pathtrace.hip, for rt_frames.cpp (the self-test: rt_abi.cpp)
 hipError_t rt_launch_math_selftest(uint32_t which, unsigned long long* mismatches, uint32_t* first_bad,
                                    hipStream_t stream);
 hipError_t rt_launch_pathtrace(const KernelArgs& ka, int mode, bool tris, bool frame_par, uint32_t threads,
@@ -46,7 +47,7 @@ hipError_t rt_launch_unpack(const float4* src, float4* accum, uint32_t* output, 
                             uint32_t tiles_x, uint32_t n_tiles, uint32_t first_rank, uint32_t ranks, uint32_t world,
                             uint64_t stride_px, uint32_t skip_rank, float divisor, hipStream_t stream);
 
-// scene_edit.hip
+// scene_edit.hip, for rt_abi.cpp (edit, refit) and rt_frames.cpp (what the triangle walks read, derived)
 hipError_t rt_launch_edit(const float* model, const uint32_t* tri_object, const uint32_t* sub_object,
                           const uint2* object_tris, const rt_scene::Placement* place, uint32_t object_count,
                           uint32_t n_tri, uint32_t n_sub, RtTriangleHot* tris, float4* bounds, RtSubObject* subs,
@@ -62,7 +63,7 @@ hipError_t rt_launch_tri_leafcert(const SubObjectPrim* prims, uint32_t n_prims, 
 hipError_t rt_launch_tri_leaftris(const SubObjectPrim* prims, uint32_t n_prims, const RtTriangleHot* tris,
                                   uint32_t n_tri, uint4* out, hipStream_t stream);
 
-// the query kernels (query.hip, occlusion.hip, radiance.hip, ambient.hip): per kernel the workgroup size of a
+// the query kernels (query.hip, occlusion.hip, radiance.hip, ambient.hip), for rt_queries.cpp: per kernel the workgroup size of a
 // placement, the resident workgroups per CU, and the launch on a schedule of rt_query_schedule.h
 uint32_t rt_query_threads(int mode, bool tris);
 hipError_t rt_query_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
@@ -111,7 +112,7 @@ hipError_t rt_launch_ambient(const KernelArgs& ka, int mode, bool tris, size_t l
                              const void* points, void* partials, uint64_t count, unsigned long long* counter,
                              uint32_t first_sample, uint32_t samples, uint32_t stripes, hipStream_t stream);
 
-// denoise.hip
+// denoise.hip, for rt_post.cpp
 hipError_t rt_launch_feature_rays(const KernelArgs& ka, uint32_t first, uint32_t count, void* rays, hipStream_t stream);
 hipError_t rt_launch_feature_resolve(const KernelArgs& ka, uint32_t first, uint32_t count, const void* rays,
                                      const void* hits, float4* plane_a, float4* plane_b, uint2* plane_i,
@@ -136,7 +137,7 @@ hipError_t rt_launch_temporal(const KernelArgs& ka, const float4* accum, const f
                               uint32_t* packed, float n, float max_history, float sigma2, float normal_min,
                               hipStream_t stream, const TemporalMotion* motion = nullptr);
 
-// display.hip
+// display.hip, for rt_post.cpp
 hipError_t rt_launch_display_meter(const float4* src, uint64_t n, float div, uint32_t* bins, hipStream_t stream);
 hipError_t rt_launch_display_solve(uint32_t* bins, uint32_t* kept, uint32_t* state, uint32_t low_permille,
                                    uint32_t high_permille, float key, float min_exposure, float max_exposure,

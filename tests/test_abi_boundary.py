@@ -12,6 +12,7 @@ import pytest
 
 from rust_gpu_raytracing_amd import _native as N
 from rust_gpu_raytracing_amd import buffers as B
+from tests import host_sources
 
 ROOT = Path(__file__).resolve().parents[1]
 HEADER = ROOT / "include" / "rt_abi.h"
@@ -56,7 +57,7 @@ def test_library_reads_no_environment():
 
 def test_tuning_keys_documented():
     """Every rt_set_tuning key the library accepts is listed in include/rt_abi.h."""
-    src = (ROOT / "rust_gpu_raytracing_amd" / "csrc" / "rt_abi.cpp").read_text()
+    src = host_sources.TUNING.read_text()
     body = src[src.index("int rt_set_tuning("):]
     body = body[:body.index("\n}\n")]
     keys = set(re.findall(r'k == "(\w+)"', body))

@@ -17,6 +17,7 @@ import pytest
 from rust_gpu_raytracing_amd import _native as N
 from rust_gpu_raytracing_amd import buffers as B
 from tests import gather_ref as G
+from tests import host_sources
 from tests.golden.fixtures import CASES, load, scene_from_inputs
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -79,10 +80,10 @@ def test_null_context_fails_cleanly(native_lib):
 
 
 def test_gather_chunk_is_a_tuning_key():
-    src = (ROOT / "rust_gpu_raytracing_amd" / "csrc" / "rt_abi.cpp").read_text()
+    src = host_sources.TUNING.read_text()
     body = src[src.index("int rt_set_tuning("):]
     assert 'k == "gather_chunk"' in body[:body.index("\n}\n")]
-    assert re.search(r"kDefaultGatherChunk = 16384;", src)
+    assert re.search(r"kDefaultGatherChunk = 16384;", host_sources.CONTEXT.read_text())
     assert '"gather_chunk" 16384' in HEADER.read_text()
 
 

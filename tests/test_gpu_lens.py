@@ -191,6 +191,26 @@ def test_radiance_of_the_lens_rays_is_the_lens_query(gpu, kind):
         assert dev.cpu().numpy().tobytes() == direct.tobytes()
 
 
+def test_host_forms_in_chunks_equal_the_device_forms(gpu):
+    """The staging of the host forms at the smallest shape at which its chunks can go wrong: a 7x5
+    image, the range first_pixel = 3, count = 29 with "query_chunk" = 8 -- four chunks, the last of
+    five pixels. rt_lens and rt_lens_rays equal their device forms on the range bit for bit, and
+    the segments equal the device form's counter."""
+    _, case, scene = golden_scene("c3")
+    cam = lens_camera(scene.camera, "perspective", aperture=0.3, focus=20.0, width=7, height=5, stream_base=1)
+    with renderer("c3", tuning={"query_chunk": 8}) as r:
+        dev, n_dev = r.lens(cam, bounces=case["bounces"], first_sample=2, samples=3, region=(3, 29), device=True,
+                            return_segments=True)
+        got, n = r.lens(cam, bounces=case["bounces"], first_sample=2, samples=3, region=(3, 29), return_segments=True)
+        dev_rays = r.lens_rays(cam, 2, region=(3, 29), device=True).cpu().numpy()
+        rays = r.lens_rays(cam, 2, region=(3, 29))
+    dev = dev.cpu().numpy()
+    assert got.shape == (29, 4) and bits(got).any() and n >= 3 * 29  # (a segment per path at least)
+    assert got.tobytes() == dev.tobytes() and n == n_dev
+    assert rays.shape == (29,) and dev_rays.shape == (29, 8) and rays.tobytes() == dev_rays.tobytes()
+    assert np.array_equal(rays["stream"], 1 + 3 + np.arange(29, dtype=np.uint32))
+
+
 # ---------------------------------------------------------------------------- side effects
 @pytest.mark.parametrize("batch", [None, 1])
 def test_lens_does_not_disturb_a_render(gpu, batch):

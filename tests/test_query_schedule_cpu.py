@@ -1,6 +1,6 @@
 """CPU check of the ray queries' launch schedule (csrc/rt_query_schedule.h).
 
-tests/cpp/query_schedule.cpp includes the header rt_abi.cpp compiles and compares query_schedule
+tests/cpp/query_schedule.cpp includes the header rt_queries.cpp compiles and compares query_schedule
 with the three formulas the query paths carried before they shared it (closest hit, any hit,
 radiance / gather), written out in the harness: counts 1, 63, 64, 65, 777, 10,000, 2^20 + 77 and
 2^32 + 5, 4 / 8 / 16 waves per workgroup, 1 / 256 / 2,048 resident workgroups, the four cap sets.
