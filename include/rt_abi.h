@@ -62,7 +62,9 @@ extern "C" {
  * 12, additive: lens queries (rt_lens, rt_lens_device, rt_lens_rays, rt_lens_rays_device,
  * rt_lens_camera);
  * 12, additive: hit-list queries (rt_trace_hits, rt_trace_hits_device, rt_pick_hits,
- * RT_HITS_MAX). */
+ * RT_HITS_MAX);
+ * 12, additive: proximity queries (rt_nearest, rt_nearest_device, rt_near_point,
+ * struct rt_nearest). */
 #define RT_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------- */
@@ -499,6 +501,102 @@ RT_API int rt_trace_hits_device(rt_ctx* ctx, const void* rays_device, void* hits
                                 void* counts_device /* may be NULL */, uint64_t count, uint32_t max_hits);
 RT_API int rt_pick_hits(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hits /* max_hits */, uint32_t* n,
                         uint32_t max_hits);
+
+/* ---- proximity queries (ABI 12, additive: proximity queries) ---------------
+ *
+ * "What is the closest surface point to this point?": snapping, clearance before a move, camera
+ * collision, distance-field bakes, picking near a 3D cursor. Every other query starts from a ray;
+ * this one starts from a point, against the same scene on the device.
+ *
+ * THE NEAREST-POINT CONTRACT. The reference has no such function, so the contract is this
+ * library's. Every operation below is one f32 operation, rounded to nearest; nothing is
+ * contracted into a fused multiply-add; division and sqrt are correctly rounded;
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z. For the point p and the bound max_distance:
+ *
+ *  1. Sphere i, centre c and radius r as uploaded (only |r| matters: hollow shells with a
+ *     negative radius are spheres of radius |r|):
+ *       v = c - p;  l = sqrt(dot(v, v));  key = | l - |r| |.
+ *     If l == 0: point = (c.x + |r|, c.y, c.z), normal = (1, 0, 0). Otherwise s = |r| / l,
+ *     point = c - v*s (per component c.k - v.k*s), normal = -(v / l) (per component -(v.k / l)).
+ *     side = l >= |r| (1: on or outside the surface). feature = 0.
+ *  2. Triangle, from the stored a, edge_ab (ab), edge_ac (ac); no vertex is rebuilt except as
+ *     written. Ericson's seven regions in this order, with the textbook's <= and >=; a comparison
+ *     with NaN is false, so the search falls through to the next region:
+ *       ap = p - a;  d1 = dot(ab, ap);  d2 = dot(ac, ap)
+ *       1 (vertex a):  d1 <= 0 && d2 <= 0:               q = a
+ *       bp = ap - ab;  d3 = dot(ab, bp);  d4 = dot(ac, bp)
+ *       2 (vertex b):  d3 >= 0 && d4 <= d3:              q = a + ab
+ *       vc = d1*d4 - d3*d2
+ *       3 (edge ab):   vc <= 0 && d1 >= 0 && d3 <= 0:    v = W(d1 / (d1 - d3));  q = a + ab*v
+ *       cp = ap - ac;  d5 = dot(ab, cp);  d6 = dot(ac, cp)
+ *       4 (vertex c):  d6 >= 0 && d5 <= d6:              q = a + ac
+ *       vb = d5*d2 - d1*d6
+ *       5 (edge ac):   vb <= 0 && d2 >= 0 && d6 <= 0:    w = W(d2 / (d2 - d6));  q = a + ac*w
+ *       va = d3*d6 - d5*d4;  e1 = d4 - d3;  e2 = d5 - d6
+ *       6 (edge bc):   va <= 0 && e1 >= 0 && e2 >= 0:    w = W(e1 / (e1 + e2));
+ *                                                        q = (a + ab*(1 - w)) + ac*w
+ *       7 (face):      denom = 1 / ((va + vb) + vc);  v = W(vb*denom);  w = W(vc*denom);
+ *                      if (w > 1 - v) w = 1 - v;         q = (a + ab*v) + ac*w
+ *     W(x) = x if 0 <= x <= 1, 1 if x > 1, else 0 (NaN included): every weight is in [0, 1], so
+ *     q is a convex combination of the vertices whatever a degenerate triangle makes of the
+ *     quotients -- that is what lets a box bound the key. A vector times a weight is one product
+ *     per component; sums are taken left to right as parenthesised.
+ *       key = sqrt(dot(q - p, q - p));  point = q;  normal = the stored face_normal, not flipped;
+ *       side = dot(calc_normal, ap) >= 0;  feature = the region number, 1..7.
+ *  3. Candidates: every sphere 0..sphere_count-1, and every triangle visit of the reference's
+ *     sweep through objects 0..object_count-1 and their sub-objects, at its sweep position as THE
+ *     HIT-LIST CONTRACT defines it (index clamps included). Object and sub-object boxes are not
+ *     part of the meaning. A primitive is a candidate iff its key is not NaN and
+ *     key <= max_distance: max_distance = +inf means "anything", a NaN or negative max_distance
+ *     gives a miss, and so do NaN coordinates.
+ *  4. Result: the candidate of the smallest key; among equal keys a triangle before a sphere (as
+ *     trace_ray prefers them), then the lower sweep position or the lower sphere index.
+ *     distance = its key. A miss is all zero apart from distance = 3.4028235e38f, as in rt_hit.
+ *  5. Domain for exactness: finite position with |position| <= 1e15, as for ray origins. Outside
+ *     it the record is unspecified; the search terminates on any input.
+ *  6. The call sees the scene as of the call and changes nothing that a render, a queued frame,
+ *     rt_ray_count, the timings or the tile schedule can observe. The result does not depend on
+ *     the brute-force mode, on any rt_set_tuning key ("query_lds_mode" and "nearest_walk"
+ *     included) or on the triangle pruning mode. It works on rank contexts.
+ *
+ * The accelerated search culls by the boxes of the sphere BVH and of the triangle accelerator
+ * with a certified lower bound. Sub-object boxes come from the caller
+ * (rt_update_sub_object_info) and carry no meaning here: while they are not known to enclose
+ * their triangles and every triangle in a finite box to be finite -- the library looks once after
+ * a triangle, sub-object or object-range upload and after rt_update_objects -- and in brute-force
+ * mode, every candidate is tested instead. The result is the same. That look is a host pass: the
+ * first rt_nearest or rt_nearest_device call after such an upload or edit, on a scene with
+ * objects, copies every triangle back to the host and waits for the stream before it launches;
+ * the calls after it do not.
+ *
+ * rt_nearest: host pointers, synchronous; staged through the pinned buffer of rt_trace_rays in
+ * chunks of "query_chunk" points. rt_nearest_device: device pointers on the context's device,
+ * 16-byte aligned; stream-ordered on rt_stream(ctx), no host copy of the records, asynchronous
+ * but for the look at the boxes described above.
+ * RT_E_INVALID: NULL points or out with count > 0; pointers that are not device memory of the
+ * context's device, or misaligned (the device form). count == 0 returns RT_OK and launches
+ * nothing. */
+typedef struct rt_near_point {
+    float position[3];
+    float max_distance;      /* candidates have key <= max_distance; +inf: anything */
+} rt_near_point;
+
+/* (a tag only: the entry point carries the same name) */
+struct rt_nearest {
+    float distance;          /* the key; 3.4028235e38f on a miss */
+    float point[3];          /* the closest surface point */
+    float normal[3];         /* sphere: outward; triangle: the stored face_normal */
+    uint32_t feature;        /* sphere: 0; triangle: the region, 1..7 */
+    uint32_t kind;           /* RT_HIT_MISS, RT_HIT_SPHERE, RT_HIT_TRIANGLE */
+    uint32_t index;          /* sphere index as uploaded, or object index */
+    uint32_t sub_object;
+    uint32_t triangle;
+    uint32_t material_index;
+    uint32_t side;           /* sphere: 1 on or outside; triangle: 1 on calc_normal's side */
+    uint32_t _reserved[2];   /* 0 */
+};
+RT_API int rt_nearest(rt_ctx* ctx, const rt_near_point* points, struct rt_nearest* out, uint64_t count);
+RT_API int rt_nearest_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count);
 
 /* ---- radiance queries (ABI 12, additive: radiance queries) -----------------
  *
@@ -1468,6 +1566,8 @@ RT_API int rt_set_triangle_pruning(rt_ctx* ctx, int mode);
  *   0..2: the highest LDS staging mode of the query, occlusion and radiance kernels, falling back as a dispatch does),
  *   "gather_chunk" 16384 (1..2^20: points per launch of rt_gather, rt_gather_device, rt_ambient and
  *   rt_ambient_device, 1 KB of partials each),
+ *   "nearest_walk" 1|0|2 (1: rt_nearest walks the accelerators, 0: its sweep instance tests every candidate,
+ *   2: the walk without the greedy descent that precedes it),
  *   "probe_chunk" 1048576 (1..2^26: paths per launch of rt_probe_sh and rt_probe_sh_device, 16 B of scratch each;
  *   a launch covers whole probes, max(1, probe_chunk / samples) of them);
  *   features and denoiser: "feature_band" 524288 (64..2^24: pixels per traced band of rt_compute_features),

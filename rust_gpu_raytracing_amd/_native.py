@@ -122,6 +122,17 @@ class rt_hit(ctypes.Structure):
                 ("sub_object", ctypes.c_uint32), ("triangle", ctypes.c_uint32), ("_reserved", ctypes.c_uint32)]
 
 
+class rt_near_point(ctypes.Structure):
+    _fields_ = [("position", ctypes.c_float * 3), ("max_distance", ctypes.c_float)]
+
+
+class rt_nearest(ctypes.Structure):
+    _fields_ = [("distance", ctypes.c_float), ("point", ctypes.c_float * 3), ("normal", ctypes.c_float * 3),
+                ("feature", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("index", ctypes.c_uint32),
+                ("sub_object", ctypes.c_uint32), ("triangle", ctypes.c_uint32), ("material_index", ctypes.c_uint32),
+                ("side", ctypes.c_uint32), ("_reserved", ctypes.c_uint32 * 2)]
+
+
 class rt_denoise_params(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("sigma_color", ctypes.c_float),
                 ("sigma_albedo", ctypes.c_float), ("sigma_depth", ctypes.c_float)]
@@ -159,6 +170,8 @@ assert ctypes.sizeof(rt_object_transform) == 32 and ctypes.sizeof(rt_motion) == 
 assert ctypes.sizeof(rt_denoise_params) == 16
 assert ctypes.sizeof(rt_query_ray) == 32 and ctypes.sizeof(rt_hit) == 64
 assert ctypes.sizeof(rt_occlusion_ray) == 32
+assert ctypes.sizeof(rt_near_point) == B.NEAR_POINT.itemsize == 16 and rt_near_point.max_distance.offset == 12
+assert ctypes.sizeof(rt_nearest) == B.NEAREST.itemsize == 64 and rt_nearest.kind.offset == 32
 assert ctypes.sizeof(rt_radiance_ray) == 32
 assert ctypes.sizeof(rt_gather_point) == 32 and rt_gather_point.stream.offset == 12 and rt_gather_point.normal.offset == 16
 assert ctypes.sizeof(rt_ambient_point) == 32 and rt_ambient_point.stream.offset == 12 and rt_ambient_point.t_max.offset == 28
@@ -207,6 +220,8 @@ SIGNATURES = {
     "rt_trace_hits": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, _U32]),
     "rt_trace_hits_device": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, _U32]),
     "rt_pick_hits": (ctypes.c_int, [_P, _U32, _U32, _P, ctypes.POINTER(_U32), _U32]),
+    "rt_nearest": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
+    "rt_nearest_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64]),
     "rt_radiance": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_radiance_device": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, _P]),
     "rt_gather": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(ctypes.c_uint64)]),

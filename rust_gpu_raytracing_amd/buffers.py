@@ -114,6 +114,12 @@ HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # rt_hit.kind
 # rt_occlusion_ray -- occlusion queries (rt_occluded): a QUERY_RAY with the distance bound in the
 # place of _pad1; the result is one uint8 per ray
 OCCLUSION_RAY = np.dtype([("origin", "<f4", 3), ("_pad0", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
+# rt_near_point / struct rt_nearest -- proximity queries (rt_nearest): a point with its distance
+# bound, and the 64-byte record of the closest surface point (kind: the HIT kinds)
+NEAR_POINT = np.dtype([("position", "<f4", 3), ("max_distance", "<f4")])
+NEAREST = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("feature", "<u4"),
+                    ("kind", "<u4"), ("index", "<u4"), ("sub_object", "<u4"), ("triangle", "<u4"),
+                    ("material_index", "<u4"), ("side", "<u4"), ("_reserved", "<u4", 2)])
 # rt_radiance_ray -- radiance queries (rt_radiance): a QUERY_RAY with the RNG stream in the place of
 # _pad0; the result is four float32 per ray
 RADIANCE_RAY = np.dtype([("origin", "<f4", 3), ("stream", "<u4"), ("direction", "<f4", 3), ("_pad1", "<f4")])

@@ -20,13 +20,13 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 INCLUDE = ROOT / "include"
 OUT = PKG / "librt_pathtrace.so"
-SOURCES = [CSRC / "pathtrace.hip", CSRC / "query.hip", CSRC / "occlusion.hip", CSRC / "hits.hip", CSRC / "ambient.hip", CSRC / "radiance.hip", CSRC / "denoise.hip",
+SOURCES = [CSRC / "pathtrace.hip", CSRC / "query.hip", CSRC / "occlusion.hip", CSRC / "hits.hip", CSRC / "nearest.hip", CSRC / "ambient.hip", CSRC / "radiance.hip", CSRC / "denoise.hip",
            CSRC / "display.hip", CSRC / "scene_edit.hip", CSRC / "rt_abi.cpp", CSRC / "rt_frames.cpp", CSRC / "rt_queries.cpp", CSRC / "rt_post.cpp",
            CSRC / "sphere_bvh.cpp", CSRC / "scene_build.cpp", CSRC / "rt_multi.cpp"]
 HEADERS = [CSRC / "rt_bvh_slab.h", CSRC / "rt_device_math.h", CSRC / "rt_kernel_args.h", CSRC / "sphere_bvh.h",
            CSRC / "rt_scene_math.h", CSRC / "tri_qnode.h", CSRC / "tri_cone.h", CSRC / "rt_path_common.h",
            CSRC / "rt_walk.h", CSRC / "rt_sphere_roots.h", CSRC / "rt_sphere_walk.h", CSRC / "rt_query_frame.h", CSRC / "rt_occlusion_walk.h",
-           CSRC / "rt_query_schedule.h", CSRC / "rt_launch.h", CSRC / "rt_ctx.h", INCLUDE / "rt_abi.h"]
+           CSRC / "rt_query_schedule.h", CSRC / "rt_nearest_math.h", CSRC / "rt_launch.h", CSRC / "rt_ctx.h", INCLUDE / "rt_abi.h"]
 
 ARCH = os.environ.get("RT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

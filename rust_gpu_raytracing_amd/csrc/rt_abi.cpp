@@ -181,6 +181,7 @@ int refresh_sphere_slots(rt_ctx* ctx, uint32_t count, bool sphere_only) {
     ctx->sphere_rmin = sl.r_min;
     ctx->sphere_rmax = sl.r_max;
     ctx->slots_dirty = false;
+    ctx->near_radius_dirty = true;  // rt_nearest's table of |radius| holds the spheres the slots were built for
     ctx->slots_count = count;
     ctx->slots_sphere_only = sphere_only;
     return RT_OK;
@@ -283,6 +284,7 @@ int upload_spheres(rt_ctx* ctx, const rt_scene_sphere* s, uint32_t n) {
     if (n == 0) return RT_OK;
     std::copy(s, s + n, ctx->h_sph.begin());
     ctx->slots_dirty = true;  // slots + BVH are rebuilt at the next dispatch
+    ctx->near_radius_dirty = true;  // rt_nearest's table of |radius| is rewritten at the next query
     return RT_OK;
 }
 
@@ -290,6 +292,7 @@ int upload_triangles(rt_ctx* ctx, const rt_scene_triangle* t, uint32_t n) {
     if (n == 0) return RT_OK;
     ctx->cones_dirty = true;
     ctx->ltris_dirty = true;
+    ctx->near_boxes = kNearBoxesUnknown;
     void* p;
     int rc = staging(ctx, (size_t)n * sizeof(RtTriangleHot), &p);
     if (rc) return rc;
@@ -542,7 +545,7 @@ void rt_destroy(rt_ctx* ctx) {
                     ctx->d_clock, ctx->d_stream, ctx->d_primary[0], ctx->d_primary[1], ctx->d_tri_qnodes,
                     ctx->d_tri_qgrid, ctx->d_tri_src8, ctx->d_tri_skip8, ctx->d_tri_bvh8, ctx->d_tri_lcert,
                     ctx->d_tri_ltris, ctx->d_brute_paths, ctx->d_brute_queue, ctx->d_brute_counts,
-                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_lens_cam, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
+                    ctx->d_query_next, ctx->d_query_buf, ctx->d_radiance_segs, ctx->d_gather_partials, ctx->d_probe_lights, ctx->d_probe_next, ctx->d_lens_cam, ctx->d_near_radius, ctx->d_feat[0], ctx->d_feat[1], ctx->d_feat_scratch,
                     ctx->d_dn[0], ctx->d_dn[1], ctx->d_dn_out, ctx->d_disp_out, ctx->d_disp_meter,
                     ctx->t_slot[0].plane[0], ctx->t_slot[0].plane[1], ctx->t_slot[0].plane[2],
                     ctx->t_slot[1].plane[0], ctx->t_slot[1].plane[1], ctx->t_slot[1].plane[2],
@@ -698,6 +701,7 @@ int rt_update_object_info(rt_ctx* ctx, const rt_object_info* objects, uint32_t c
         ranges |= a.first_sub_object_index != b.first_sub_object_index || a.sub_object_count != b.sub_object_count;
     }
     if (boxes || ranges) ctx->tri_dirty = true;
+    if (ranges) ctx->near_boxes = kNearBoxesUnknown;
     if (ranges) ctx->models_valid = false;
     return upload_raw(ctx, ctx->d_obj, objects, (size_t)count * 48);
 }
@@ -721,6 +725,7 @@ int rt_update_sub_object_info(rt_ctx* ctx, const rt_sub_object_info* sub_objects
             saved[i].triangle_count != sub_objects[i].triangle_count)
             ctx->models_valid = false;  // the device edit path's triangle maps are stale
     ctx->tri_dirty = true;
+    ctx->near_boxes = kNearBoxesUnknown;
     return upload_raw(ctx, ctx->d_sub, sub_objects, (size_t)count * 32);
 }
 
@@ -825,6 +830,9 @@ int rt_update_objects(rt_ctx* ctx, const rt_object_transform* transforms, uint32
                                count, ctx->model_tris, (uint32_t)ctx->h_sub.size(), ctx->d_tri, ctx->d_tri_bounds,
                                ctx->d_sub, ctx->d_obj, ctx->stream));
     ctx->geom_on_device = true;
+    // the edit rewrites triangles and boxes on the device (a placement may make them non-finite):
+    // rt_nearest looks at them again before it culls by them
+    ctx->near_boxes = kNearBoxesUnknown;
     // the accelerator keeps its topology; its boxes (and the margin extent) follow the new bounds
     if (ctx->d_tri_bvh && ctx->tri_nodes && !ctx->tri_dirty) {
         RT_HIP(ctx, rt_launch_refit(ctx->d_tri_bvh, ctx->d_tri_prims, ctx->d_sub, ctx->d_tri_order,
@@ -1035,6 +1043,8 @@ int rt_set_tuning(rt_ctx* ctx, const char* key, int32_t value) {
         if ((rc = range(1, (int32_t)kMaxGatherChunk)) == RT_OK) ctx->gather_chunk = (uint32_t)v;
     } else if (k == "probe_chunk") {
         if ((rc = range(1, (int32_t)kMaxProbeChunk)) == RT_OK) ctx->probe_chunk = (uint32_t)v;
+    } else if (k == "nearest_walk") {
+        if ((rc = range(0, 2)) == RT_OK) ctx->nearest_walk = v;
     } else if (k == "query_lds_mode") {
         if ((rc = range(-1, 2)) == RT_OK) ctx->query_lds_mode = v;
     } else if (k == "feature_band") {

@@ -57,6 +57,8 @@ constexpr uint32_t kMaxProbeChunk = 1u << 26;
 // the frame (3840x2160 would take 800 MB at once); tuning "feature_band".
 constexpr uint32_t kDefaultFeatureBand = 1u << 19;
 constexpr uint32_t kMaxFeatureBand = 1u << 24;
+// rt_ctx::near_boxes
+constexpr int kNearBoxesUnknown = 0, kNearBoxesVouched = 1, kNearBoxesRefuted = 2;
 
 }  // namespace rth
 
@@ -304,6 +306,15 @@ struct rt_ctx {
     size_t probe_lights_bytes = 0;
     unsigned long long* d_probe_next = nullptr;     // the chunk counters of the two launches in flight
     uint4* d_lens_cam = nullptr;                    // rt_lens: the descriptor the launches of a call read
+    // proximity queries (rt_nearest; nearest.hip)
+    int nearest_walk = 1;                           // tuning "nearest_walk" 0: the sweep instance, 2: the walk without its descent
+    float* d_near_radius = nullptr;                 // |radius| as uploaded, by original sphere index
+    size_t near_radius_bytes = 0;
+    bool near_radius_dirty = true;                  // the sphere slots were rebuilt since the table was written
+    // whether every non-empty sub-object box encloses its triangles within the margin of the walk's
+    // bound (rt_nearest_math.h): established by one host pass, until the next triangle, sub-object
+    // or object-range upload
+    int near_boxes = 0;                             // kNearBoxes*
     struct QueryOccKey {                        // the last query instance (kind: which kernel's, QueryKind)
         int mode = -1, kind = 0;
         uint32_t tris = 0, lds_bytes = 0;

@@ -82,6 +82,13 @@ hipError_t rt_hits_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_
 hipError_t rt_launch_hits(const KernelArgs& ka, int mode, bool tris, size_t lds_bytes, const rtq::QuerySchedule& s,
                           const void* rays, void* hits, void* counts, uint64_t count, uint32_t max_hits, bool pick,
                           unsigned long long* counter, hipStream_t stream);
+// nearest.hip: `sweep`: the instance that tests every candidate; `radius`: |radius| by original sphere
+// index; `descend`: the walk instance makes its greedy descent before each walk
+uint32_t rt_nearest_threads(int mode, bool tris);
+hipError_t rt_nearest_occupancy(int mode, bool tris, bool sweep, size_t lds_bytes, int* blocks_per_cu);
+hipError_t rt_launch_nearest(const KernelArgs& ka, int mode, bool tris, bool sweep, size_t lds_bytes,
+                             const rtq::QuerySchedule& s, const void* points, void* out, const float* radius,
+                             bool descend, uint64_t count, unsigned long long* counter, hipStream_t stream);
 uint32_t rt_radiance_threads(int mode, bool tris);
 hipError_t rt_radiance_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
 hipError_t rt_gather_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);

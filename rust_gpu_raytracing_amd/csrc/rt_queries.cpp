@@ -1,14 +1,15 @@
 // rt_queries.cpp — the query families of include/rt_abi.h, host and device forms.
 //
 // rt_trace_rays, rt_pick, rt_occluded, rt_trace_hits, rt_pick_hits, rt_radiance, rt_gather,
-// rt_ambient, rt_probe_sh, rt_lens and rt_lens_rays: one descriptor-driven path (QueryFamily,
-// staged_query, device_query) around each family's run. It launches query.hip, occlusion.hip,
-// hits.hip, radiance.hip and ambient.hip.
+// rt_ambient, rt_probe_sh, rt_lens, rt_lens_rays and rt_nearest: one descriptor-driven path
+// (QueryFamily, staged_query, device_query) around each family's run. It launches query.hip,
+// occlusion.hip, hits.hip, radiance.hip, ambient.hip and nearest.hip.
 #include <algorithm>
 #include <cmath>
 
 #include "rt_ctx.h"
 #include "rt_launch.h"
+#include "rt_nearest_math.h"
 #include "rt_query_schedule.h"
 
 namespace {
@@ -48,7 +49,8 @@ int rth::query_enter(rt_ctx* ctx) {
 // rt_radiance_kernel (radiance.hip), whose `count` is its walks' lower bound, rays x samples, or
 // its gather instance (points x samples) or its probe instance (probes x samples), or
 // rt_ambient_kernel (ambient.hip; points x samples), or the radiance kernel's lens instance
-// (pixels x samples), or rt_hits_kernel (hits.hip).
+// (pixels x samples), or rt_hits_kernel (hits.hip), or rt_nearest_kernel (nearest.hip), its walk
+// instance or its sweep instance.
 enum QueryKind {
     kQueryClosest = 0,
     kQueryAnyHit = 1,
@@ -57,21 +59,32 @@ enum QueryKind {
     kQueryProbe = 4,
     kQueryAmbient = 5,
     kQueryLens = 6,
-    kQueryHits = 7
+    kQueryHits = 7,
+    kQueryNearest = 8,
+    kQueryNearestSweep = 9
 };
+
+static hipError_t nearest_walk_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return rt_nearest_occupancy(mode, tris, false, lds_bytes, blocks_per_cu);
+}
+static hipError_t nearest_sweep_occupancy(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu) {
+    return rt_nearest_occupancy(mode, tris, true, lds_bytes, blocks_per_cu);
+}
 
 // Per kind: the workgroup size of the instance for a placement, and its resident workgroups per CU.
 static const struct {
     uint32_t (*threads)(int mode, bool tris);
     hipError_t (*occupancy)(int mode, bool tris, size_t lds_bytes, int* blocks_per_cu);
-} kQueryKernels[8] = {{rt_query_threads, rt_query_occupancy},
+} kQueryKernels[10] = {{rt_query_threads, rt_query_occupancy},
                       {rt_occlusion_threads, rt_occlusion_occupancy},
                       {rt_radiance_threads, rt_radiance_occupancy},
                       {rt_radiance_threads, rt_gather_occupancy},
                       {rt_radiance_threads, rt_probe_occupancy},
                       {rt_ambient_threads, rt_ambient_occupancy},
                       {rt_radiance_threads, rt_lens_occupancy},
-                      {rt_hits_threads, rt_hits_occupancy}};
+                      {rt_hits_threads, rt_hits_occupancy},
+                      {rt_nearest_threads, nearest_walk_occupancy},
+                      {rt_nearest_threads, nearest_sweep_occupancy}};
 
 struct QueryLaunch {
     KernelArgs ka{};
@@ -408,6 +421,104 @@ int rt_pick_hits(rt_ctx* ctx, uint32_t x, uint32_t y, rt_hit* hits, uint32_t* n,
     std::memcpy(hits, h_out, list_bytes);
     std::memcpy(n, h_out + list_bytes, sizeof(uint32_t));
     return RT_OK;
+}
+
+// ---- proximity queries (nearest.hip) -----------------------------------------------------------
+//
+// Per point the closest surface point under THE NEAREST-POINT CONTRACT (include/rt_abi.h), with
+// the scene visibility and the absence of side effects of the calls above.
+
+// The table of |radius| as uploaded, by original sphere index, that the kernel's keys read (the
+// slots hold radius * radius): rewritten after every sphere upload, and after a rebuild of the
+// slots for another sphere count (it holds the first slots_count spheres of h_sph).
+static int refresh_near_radius(rt_ctx* ctx) {
+    const uint32_t n = ctx->slots_count == 0xffffffffu ? 0u : ctx->slots_count;
+    if (ctx->d_near_radius && !ctx->near_radius_dirty) return RT_OK;
+    int rc = grow_buffer(ctx, "nearest radii", &ctx->d_near_radius, &ctx->near_radius_bytes,
+                         (size_t)std::max<uint32_t>(ctx->cap_sph, 1u) * sizeof(float));
+    if (rc) return rc;
+    std::vector<float> r(n);
+    for (uint32_t i = 0; i < n; i++) r[i] = std::fabs(ctx->h_sph[i].radius);
+    if ((rc = upload_raw(ctx, ctx->d_near_radius, r.data(), (size_t)n * sizeof(float)))) return rc;
+    ctx->near_radius_dirty = false;
+    return RT_OK;
+}
+
+// Whether the walk may cull by the triangle accelerator's boxes: every non-empty sub-object box
+// that the sweep visits encloses a, fl(a + ab) and fl(a + ac) of its triangles within the margin,
+// and no triangle in a finite box has a non-finite component (rtn::box_holds_triangle). One pass
+// over the device's sub-objects and triangles, read back: the first query after a triangle,
+// sub-object or object-range upload or a device edit copies every triangle to the host and waits
+// for the stream, the device form included.
+static int vouch_near_boxes(rt_ctx* ctx) {
+    if (ctx->near_boxes != kNearBoxesUnknown) return RT_OK;
+    int rc = sync_host_geometry(ctx);
+    if (rc) return rc;
+    const uint32_t n_tri = ctx->n_tri_dev;
+    std::vector<RtTriangleHot> hot(n_tri);
+    RT_HIP(ctx, hipMemcpyAsync(hot.data(), ctx->d_tri, (size_t)n_tri * sizeof(RtTriangleHot), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    bool ok = true;
+    for (size_t o = 0; o < ctx->h_obj.size() && ok; o++) {
+        const rt_object_info& ob = ctx->h_obj[o];
+        for (uint32_t i = 0; i < ob.sub_object_count && ok; i++) {
+            const size_t si = (size_t)ob.first_sub_object_index + i;
+            if (si >= ctx->h_sub.size()) break;  // validated on upload; never taken
+            const rt_sub_object_info& sub = ctx->h_sub[si];
+            for (uint32_t j = 0; j < sub.triangle_count && ok; j++) {
+                const size_t ti = (size_t)sub.first_triangle_index + j;
+                if (ti >= n_tri) {  // the kernel clamps the index: another sub-object's triangle
+                    ok = false;
+                    break;
+                }
+                float a[3], ab[3], ac[3], cn[3], fn[3];
+                unpack_triangle(hot[ti], a, ab, ac, cn, fn);
+                ok = rtn::box_holds_triangle(sub.min_bounds, sub.max_bounds, rtn::v3(a[0], a[1], a[2]),
+                                             rtn::v3(ab[0], ab[1], ab[2]), rtn::v3(ac[0], ac[1], ac[2]));
+            }
+        }
+    }
+    ctx->near_boxes = ok ? kNearBoxesVouched : kNearBoxesRefuted;
+    return RT_OK;
+}
+
+// Answers `count` rt_near_point at device pointer `points` into rt_nearest records at `out`,
+// stream-ordered on the primary stream. The sweep instance runs in brute-force mode, with tuning
+// "nearest_walk" 0, and while the sub-object boxes are not vouched for; "nearest_walk" 2 is the walk
+// without its greedy descent.
+static int run_nearest(rt_ctx* ctx, const void* points, void* out, uint64_t count) {
+    if (count == 0) return RT_OK;
+    int rc = refresh_near_radius(ctx);
+    if (rc) return rc;
+    bool sweep = ctx->brute != 0 || ctx->nearest_walk == 0;
+    if (!sweep && ctx->params.object_count != 0 && ctx->use_tri_bvh) {
+        if ((rc = vouch_near_boxes(ctx))) return rc;
+        sweep = ctx->near_boxes != kNearBoxesVouched;
+    }
+    QueryLaunch q;
+    if ((rc = query_scene(ctx, count, sweep ? kQueryNearestSweep : kQueryNearest, q))) return rc;
+    // every chunk from the counter, as the closest-hit kernel takes them
+    const rtq::QuerySchedule s = rtq::query_schedule(count, q.waves_per_block, q.resident, 0u, rtq::kWalkChunkMax);
+    RT_HIP(ctx, hipMemsetAsync(ctx->d_query_next, 0, sizeof(unsigned long long), ctx->stream));
+    const hipError_t e = rt_launch_nearest(q.ka, q.sl.mode, q.sl.tris, sweep, q.lds_bytes, s, points, out,
+                                           ctx->d_near_radius, ctx->nearest_walk == 1, count, ctx->d_query_next,
+                                           ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, "rt_nearest_kernel launch", e);
+    return RT_OK;
+}
+
+static_assert(sizeof(rt_near_point) == 16 && sizeof(struct rt_nearest) == 64, "proximity record layouts");
+constexpr QueryFamily kNearest = {"rt_nearest", "rt_nearest_device", "points", "out", sizeof(rt_near_point),
+                                  sizeof(struct rt_nearest), 16, 0, false};
+
+int rt_nearest_device(rt_ctx* ctx, const void* points_device, void* out_device, uint64_t count) {
+    return device_query(ctx, kNearest, points_device, out_device, count, 0, nullptr,
+                        [=](const void* in, void* out, uint64_t n, unsigned long long*) { return run_nearest(ctx, in, out, n); });
+}
+
+int rt_nearest(rt_ctx* ctx, const rt_near_point* points, struct rt_nearest* out, uint64_t count) {
+    return staged_query(ctx, kNearest, points, out, count, 0, nullptr,
+                        [=](const void* in, void* d_out, uint64_t n, unsigned long long*) { return run_nearest(ctx, in, d_out, n); });
 }
 
 // ---- radiance queries (radiance.hip) -----------------------------------------------------------

@@ -470,6 +470,44 @@ class Renderer:
         self._call("rt_trace_hits", N.ptr(rays), N.ptr(hits), N.ptr(counts), rays.shape[0], max_hits)
         return hits, counts
 
+    # ------------------------------------------------------------------ proximity queries
+    def nearest(self, points, max_distance=None):
+        """The closest surface point to every point (rt_nearest; THE NEAREST-POINT CONTRACT in
+        include/rt_abi.h): over every sphere and every triangle of the scene as it is now, within
+        ``max_distance`` of the point, without touching anything a render reads.
+
+        ``points``: an (n, 3) float32 array with ``max_distance`` a scalar or an (n,) array (None:
+        +inf, "anything"); an (n, 4) array (position, max_distance); or a ``buffers.NEAR_POINT``
+        array. Returns a ``buffers.NEAREST`` array. A CUDA torch tensor of shape (n, 4) float32
+        (rt_near_point records) goes through rt_nearest_device instead -- no host round trip,
+        stream-ordered on the context's stream -- and returns a CUDA (n, 16) int32 tensor of
+        rt_nearest records."""
+        if not isinstance(points, np.ndarray) and hasattr(points, "is_cuda"):
+            if max_distance is not None:
+                raise ValueError("device points carry max_distance in their last column")
+            return self._device_query("rt_nearest_device", points, 4, "points", (16,), "int32", call_empty=False)
+        points = np.asarray(points)
+        if points.dtype == B.NEAR_POINT:
+            if max_distance is not None:
+                raise ValueError("NEAR_POINT records carry their own max_distance")
+        else:
+            r = np.ascontiguousarray(points, np.float32)
+            if r.ndim != 2 or r.shape[1] not in (3, 4) or (r.shape[1] == 4 and max_distance is not None):
+                raise ValueError("points must be (n, 4) float32, (n, 3) float32 with max_distance, or a NEAR_POINT array")
+            points = np.zeros(r.shape[0], B.NEAR_POINT)
+            points["position"] = r[:, :3]
+            if r.shape[1] == 4:
+                points["max_distance"] = r[:, 3]
+            else:
+                bound = np.asarray(np.inf if max_distance is None else max_distance, np.float32)
+                if bound.ndim > 1 or (bound.ndim == 1 and bound.shape[0] != r.shape[0]):
+                    raise ValueError("max_distance must be a scalar or an (n,) array")
+                points["max_distance"] = bound
+        points = np.ascontiguousarray(points.reshape(-1))
+        out = np.zeros(points.shape[0], B.NEAREST)
+        self._call("rt_nearest", N.ptr(points), N.ptr(out), points.shape[0])
+        return out
+
     def pick_hits(self, x: int, y: int, max_hits: int = 4) -> np.ndarray:
         """The hits of pixel (x, y)'s un-jittered camera ray, nearest first (rt_pick_hits): the
         valid records of that ray's list, at most ``max_hits`` of them."""

@@ -1,7 +1,7 @@
 """Throughput of the ray-query kernel (rt_trace_rays_device) and its placement crossover.
 
 usage: python tools/query_bench.py [--config c2_rtiow] [--width 1920 --height 1080]
-                                   [--reps 20] [--sweep] [--occluded] [--hits] [--radiance] [--gather] [--probe] [--ambient]
+                                   [--reps 20] [--sweep] [--occluded] [--hits] [--nearest] [--radiance] [--gather] [--probe] [--ambient]
                                    [--lens]
                                    [--out profiles/query_bench.jsonl]
 
@@ -30,6 +30,13 @@ the same process: the camera rays with t_max = +inf at max_hi
 to rt_trace_rays_device, the yardstick. Entry 0 of every list is checked against the closest-hit
 record. Device events around `reps` launches on the context's stream; the series alternate over
 --rounds rounds; median, minimum and maximum Mray/s per series, and the mean count per ray.
+--nearest: the proximity kernel (rt_nearest_device) beside the closest-hit call in
+the same process: one point per camera ray, off the ray's first hit by 2^-10 .. 1 along the normal
+(rays that miss: a point 10 along the ray), max_distance = +inf; the accelerated walk on all of
+them, the sweep instance (tuning "nearest_walk" 0) on the first --sweep-points of them and the walk
+without its greedy descent ("nearest_walk" 2) on all of them, whose records are checked against
+the walk's. Device events around `reps` launches (a tenth of them for
+the sweep); the series alternate over --rounds rounds; median, minimum and maximum Mitems/s.
 --radiance: the radiance kernel (rt_radiance_device) against the frame it reproduces, in one process
 (DESIGN.md §5.4e). The frame's own rays -- camera origin, each pixel's direction, stream = pixel
 index, samples = 1 -- are submitted as one batch; the yardstick is the same context rendering one
@@ -229,6 +236,73 @@ def hits_bench(r, args, q, dev, emit):
              mray_s=round(float(np.median(v)), 1), mray_s_min=round(min(v), 1), mray_s_max=round(max(v), 1),
              ms=round(n / float(np.median(v)) / 1e3, 4),
              mean_count=None if name not in mean_count else round(mean_count[name], 3), build=r._lib.rt_build_hash().decode())
+
+
+def nearest_bench(r, args, q, dev, emit):
+    """The --nearest series (module docstring)."""
+    import torch
+
+    n = q.shape[0]
+    P = ctypes.c_void_p
+    rays_t = torch.from_numpy(q.view(np.float32).reshape(-1, 8)).to(dev)
+    closest_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()  # uploaded on torch's stream, read on the context's
+    r._call("rt_trace_rays_device", P(rays_t.data_ptr()), P(closest_t.data_ptr()), n)
+    r.synchronize()
+    h = closest_t.cpu().numpy().view(B.HIT).reshape(-1)
+    hit = h["kind"] != B.HIT_MISS
+    rng = np.random.default_rng(2024)
+    pts = np.zeros(n, B.NEAR_POINT)
+    # off the first hits by 2^-10 .. 1 along the normal; rays that miss: a point 10 along the ray
+    off = np.exp2(rng.uniform(-10, 0, n)).astype(np.float32)
+    pts["position"] = np.where(hit[:, None], h["position"] + off[:, None] * h["normal"],
+                               q["origin"] + np.float32(10) * q["direction"])
+    pts["max_distance"] = np.inf
+    m = min(n, args.sweep_points)
+    pts_t = torch.from_numpy(pts.view(np.float32).reshape(-1, 4)).to(dev)
+    out_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    few_t = torch.empty((m, 16), dtype=torch.int32, device=dev)
+    plain_t = torch.empty((n, 16), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    stream = torch.cuda.ExternalStream(r.stream_handle, device=dev)
+
+    def launch(name):
+        if name == "a_closest_hit":
+            r._call("rt_trace_rays_device", P(rays_t.data_ptr()), P(closest_t.data_ptr()), n)
+        elif name == "b_nearest_walk":
+            r._call("rt_nearest_device", P(pts_t.data_ptr()), P(out_t.data_ptr()), n)
+        elif name == "d_nearest_plain_walk":  # the skip walk without the greedy descent before it
+            r.set_tuning("nearest_walk", 2)
+            r._call("rt_nearest_device", P(pts_t.data_ptr()), P(plain_t.data_ptr()), n)
+            r.set_tuning("nearest_walk", 1)
+        else:  # the sweep instance, on the first m points (every candidate per point)
+            r.set_tuning("nearest_walk", 0)
+            r._call("rt_nearest_device", P(pts_t.data_ptr()), P(few_t.data_ptr()), m)
+            r.set_tuning("nearest_walk", 1)
+
+    series = {"a_closest_hit": n, "b_nearest_walk": n, "c_nearest_sweep": m, "d_nearest_plain_walk": n}
+    for name in series:  # warm-up and a check of what is timed
+        launch(name)
+    r.synchronize()
+    assert torch.equal(out_t[:m], few_t), "the walk and the sweep disagree"
+    assert torch.equal(out_t, plain_t), "the walks with and without the descent disagree"
+    found = float((out_t[:, 8] != 0).float().mean().item())
+    rates = {name: [] for name in series}
+    for _ in range(args.rounds):
+        for name, count in series.items():
+            reps = args.reps if name != "c_nearest_sweep" else max(1, args.reps // 10)
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            for _ in range(reps):
+                launch(name)
+            t1.record(stream)
+            t1.synchronize()
+            rates[name].append(count * reps / (t0.elapsed_time(t1) * 1e-3) / 1e6)
+    for name, v in rates.items():
+        emit(kind="nearest", series=name, items=series[name], rounds=args.rounds, reps=args.reps,
+             mitems_s=round(float(np.median(v)), 4), mitems_s_min=round(min(v), 4), mitems_s_max=round(max(v), 4),
+             ms=round(series[name] / float(np.median(v)) / 1e3, 4), found_fraction=round(found, 4),
+             build=r._lib.rt_build_hash().decode())
 
 
 def radiance_bench(r, args, scene, bounces, dev, emit):
@@ -789,6 +863,8 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--occluded", action="store_true", help="the occlusion kernel against the closest-hit call")
     ap.add_argument("--hits", action="store_true", help="the hit-list kernel against the closest-hit call")
+    ap.add_argument("--nearest", action="store_true", help="the proximity kernel, walk and sweep, beside the closest-hit call")
+    ap.add_argument("--sweep-points", type=int, default=16384, help="--nearest: points of the sweep series")
     ap.add_argument("--radiance", action="store_true", help="the radiance kernel against a frame of the same rays")
     ap.add_argument("--gather", action="store_true", help="the gather query against the same paths done by hand")
     ap.add_argument("--probe", action="store_true", help="the probe query against the same paths done by hand")
@@ -857,6 +933,8 @@ def main():
             occlusion_bench(r, args, q, dev, emit)
         elif args.hits:
             hits_bench(r, args, q, dev, emit)
+        elif args.nearest:
+            nearest_bench(r, args, q, dev, emit)
         elif args.sweep:
             sizes = [s for s in (64, 256, 1024, 4096, 8192, 16384, 32768, 65536, 131072, 262144, 1048576) if s < n] + [n]
             for m in sizes:
